@@ -2,6 +2,7 @@
 """bench.py — PostCal exhaustive sweep on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload syn1000c3]
+                    [--dump-outputs DIR] [--full]
 
 A step is one full exhaustive sweep of the locus (every causal configuration,
 postcal.cpp:716-1092) plus, for N > 1, the single RCCL all-gather + merge of
@@ -10,7 +11,13 @@ GPU under torch.distributed.run); the total work per step is fixed, so the
 scaling is "strong".  Inputs are resident in HBM before the timed region.
 
 Prints ONE JSON line on rank 0 (contract in the task statement), including
-`roofline` for the dominant kernel (k_sweep<3>) and `cpu_baseline` (the
+`roofline` for the dominant kernel (k_sweep<3>).  A plain run sets up, warms
+up, times the K steps and prints the line.  --dump-outputs DIR also writes the
+last timed step's accumulators (what a caller of the pass reads back) as
+DIR/<name>.npy, float64; the inputs are seeded, so two builds can be compared
+output for output.  --full adds the side measurements, each a run of its own
+after the timed region: `single_pass_ms`, `pcie_inclusive`, the SSS and
+configs-file probes, the drop-in CLI on tests/example, and `cpu_baseline` (the
 oracle's literal N x N restatement of the reference algorithm timed on the host
 cores on a bounded sample of the same workload, rank 0 at N = 1 only).
 """
@@ -696,7 +703,14 @@ def main():
     ap.add_argument("--workload", default="syn1000c3", choices=sorted(WORKLOADS))
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=15.0)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's accumulators as DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements (single pass, PCIe-inclusive, SSS, configs file, "
+                         "tests/example CLI, CPU baselines); --no-cpu-baseline and --cpu-budget apply here")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     # integrity: a timing-ablation switch (results wrong) never produces a line
     ablate = sorted(k for k in os.environ if k.startswith("PSX_ABLATE"))
     if ablate:
@@ -861,12 +875,14 @@ def main():
         elapsed = float(x.item())
     tm = pc.timing()
     torch.cuda.synchronize()
-    mine_view = pc.partials_tensor() if use_dist else None
-    single_pass_ms = single_passes() if use_async else None  # after the timed region (and its timing)
+    # the last timed step's results, read before any side measurement runs on the handle
     acc = pc.accum() if (world == 1 or rank == 0) else None
+    mine_view = pc.partials_tensor() if use_dist else None
+    # after the timed region (and its timing)
+    single_pass_ms = single_passes() if use_async and args.full else None
 
     sss_line = None
-    if use_dist:  # after the timed region; a failure here must not lose the bench line
+    if use_dist and args.full:  # after the timed region; a failure here must not lose the bench line
         try:
             sss_line = sss_probe_sharded(rank, world, backend)
         except Exception as ex:  # noqa: BLE001
@@ -876,6 +892,12 @@ def main():
         print(f"bench: configurations checked {None if acc is None else acc.n_configs} != "
               f"{configs_per_step} per step; no line", file=sys.stderr)
         sys.exit(5)
+    if rank == 0 and args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name in ("post", "no_causal", "shared", "shared_ll", "notshared_ll"):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.asarray(getattr(acc, name), dtype=np.float64))
+        np.save(os.path.join(args.dump_outputs, "total.npy"), np.array([acc.total], dtype=np.float64))
+        np.save(os.path.join(args.dump_outputs, "n_configs.npy"), np.array([acc.n_configs], dtype=np.float64))
     if rank == 0:
         value = configs_per_step * args.steps / elapsed
         avg_kernel_s = (kms / max(launches, 1)) / 1e3
@@ -958,10 +980,6 @@ def main():
             "setup": {"synthetic_locus_s": t_synth, "gpu_model_setup_and_create_ms": pc.setup_info["setup_ms"],
                       "psd_added": pc.setup_info["psd_added"], "eigen_route": pc.setup_info["eigen_route"]},
             "pass_mode": "async (no host sync per step)" if use_async else "synchronous",
-            "single_pass_ms": single_pass_ms,
-            "single_pass_note": "one pass of this rank's shard from the host call to merged accumulators "
-                                "(psx_run_exhaustive_async + exchange + psx_sync, nothing overlapping), median of "
-                                "15, max over ranks; setup excluded — the latency of sweeping one locus once",
             # CUs kept for the merges / exchange beside overlapped passes (one XCD
             # at world >= 8 by default, PSX_OVERLAP overrides; 0: not overlapped)
             "overlap_reserved_cus": pc.overlap_cus(),
@@ -971,9 +989,14 @@ def main():
             # every engine environment knob in force (plan shape, overlap, sync mode)
             "env_knobs": {k: v for k, v in sorted(os.environ.items()) if k.startswith("PSX_")},
         }
-        if use_dist:
+        if args.full:
+            out["single_pass_ms"] = single_pass_ms
+            out["single_pass_note"] = ("one pass of this rank's shard from the host call to merged accumulators "
+                                       "(psx_run_exhaustive_async + exchange + psx_sync, nothing overlapping), median "
+                                       "of 15, max over ranks; setup excluded — the latency of sweeping one locus once")
+        if args.full and use_dist:
             out["sss"] = sss_line
-        else:
+        elif args.full:
             out["pcie_inclusive"] = pcie_inclusive(seam, configs_per_step, local)
             out["sss"] = sss_probe()
             try:

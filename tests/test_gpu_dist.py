@@ -26,7 +26,8 @@ def test_bench_sharded_two_ranks(gpu, world):
     env = dict(os.environ, PSX_DIST_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", str(world), "--steps", "2", "--warmup", "1", "--workload", "syn200c2", "--no-cpu-baseline"]
+           "--gpus", str(world), "--steps", "2", "--warmup", "1", "--workload", "syn200c2", "--full",
+           "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = r.stdout.splitlines()
@@ -50,7 +51,7 @@ def test_bench_rccl_path_world1(gpu):
     env.pop("PSX_DIST_BACKEND", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "syn200c2", "--no-cpu-baseline"]
+           "--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "syn200c2", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = r.stdout.splitlines()

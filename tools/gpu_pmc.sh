@@ -10,7 +10,7 @@ WL=${WL:-syn1000c3}
 OUT=gpurun_out/$TAG/pmc
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-CMD="python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --workload $WL"
+CMD="python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --workload $WL"
 
 
 i=0

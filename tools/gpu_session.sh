@@ -27,10 +27,10 @@ if [ -n "${AB:-}" ]; then
     cp gpurun_out/ab/abn.txt "$OUT/abn.txt"
 fi
 if [ -z "${NOBENCH:-}" ]; then
-    timeout -k 10 300 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || exit $?
+    timeout -k 10 300 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || exit $?
 fi
 if [ -n "${PROF:-}" ]; then
-    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- python3 bench.py --no-cpu-baseline > "$OUT/prof.log" 2>&1 || exit $?
+    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- python3 bench.py --full --no-cpu-baseline > "$OUT/prof.log" 2>&1 || exit $?
 fi
 if [ -n "${PMC:-}" ]; then TAG=${TAG:-s} bash tools/gpu_pmc.sh || exit $?; fi
 if [ -n "${POST:-}" ]; then
