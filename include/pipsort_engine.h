@@ -46,7 +46,8 @@ typedef struct {
     const double *s_prime;          /* [N = sum m] S_LONG_VEC after the low-rank transform       */
     int32_t n_union;                /* unionSnpCount = rows of the snp map                       */
     const int32_t *union_to_local;  /* [n_studies][n_union] idx_to_snp_map, -1 = absent          */
-    int32_t max_causal;             /* MAX_causal (-c)                                           */
+    int32_t max_causal;             /* MAX_causal (-c), 0..10 (PSX_ERANGE otherwise); the SSS    */
+                                    /* walk and -b rows serve at most 6 causal union SNPs        */
     const int32_t *sample_sizes;    /* [n_studies] (-n)                                          */
     double sharing_param;           /* -p */
     double gamma;                   /* -g */
@@ -221,7 +222,9 @@ int psx_sync(psx_engine *e, int32_t *exact_needed);
 int psx_run_configs(psx_engine *e, const int16_t *rows, int64_t n_rows, int32_t n_groups);
 
 /* PostCal::sss_computeTotalLikelihood (sss_postcal.cpp:102-380): stochastic
- * shotgun search, host random walk (mt19937(12345)) + GPU neighbour batches. */
+ * shotgun search, host random walk (mt19937(12345)) + GPU neighbour batches.
+ * The walk (set keys, iteration state, neighbour kernels) is sized for at most
+ * 6 causal SNPs: PSX_ERANGE on a handle created with max_causal 7..10. */
 int psx_run_sss(psx_engine *e, int32_t *iterations_out);
 
 /* All-gather callback of the sharded SSS walk: gather `bytes` host bytes from
@@ -250,7 +253,9 @@ typedef int (*psx_allgather_dev_fn)(void *ctx, const void *device_send, void *de
 int psx_run_sss_sharded_dev(psx_engine *e, psx_allgather_dev_fn allgather, void *ctx, int32_t *iterations_out);
 
 /* PostCal::expand_and_compute_lkl (sss_postcal.cpp:447-685), batched: evaluate
- * n_sets union sets (ascending union indices, -1 padded to `stride`), return the
+ * n_sets union sets (ascending union indices, -1 padded to `stride`, 1 <= stride
+ * <= 10: rows of up to 6 entries run the one-wave evaluator, rows of 7..10
+ * entries the wide-set kernels, one workgroup per set), return the
  * SSS score (pattern L with largest |L|, sss_postcal.cpp:624-626) per set and,
  * if accumulate != 0, add every pattern into the accumulators.  Padding may sit
  * anywhere in a row; an all -1 row is the null configuration.  psx_get_timing

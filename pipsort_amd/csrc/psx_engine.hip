@@ -30,6 +30,7 @@
 #include "psx_sweep_dev.h"
 #include "psx_mem.h"
 #include "psx_wave.h"
+#include "psx_wide.h"
 
 extern "C" __device__ __attribute__((const)) double __ockl_wfred_min_f64(double);
 
@@ -937,6 +938,8 @@ struct psx_engine {
     double L0 = 0;            // null configuration L' (K excluded), postcal.cpp:797-803
     double dval[2] = {0, 0};
     DevProb dp;
+    psx::WideProb wp;  // the same problem for the wide evaluator (sets of 7 .. PSX_KWIDE members)
+    unsigned long long* wtrace = nullptr;  // PSX_WIDE_TRACE: block 0's phase clocks (pinned host)
     // device buffers
     double* dG[2] = {nullptr, nullptr};
     double* dAd[2] = {nullptr, nullptr};
@@ -1066,6 +1069,7 @@ psx_engine::~psx_engine() {
     if (stage_ev) { hipEventSynchronize(stage_ev); hipEventDestroy(stage_ev); }
     if (hstage) psx::hfree(hstage);
     if (hbclk) psx::hfree(hbclk);
+    if (wtrace) psx::hfree(wtrace);
     if (hscore) psx::hfree(hscore);
     psx::dfree(dgen); psx::dfree(dgcsr); psx::dfree(dbm); psx::dfree(gscratch.p); psx::dfree(dscore); psx::dfree(dsrec); psx::dfree(dmrec); psx::dfree(dpass); psx::dfree(dspart); psx::dfree(dapart); psx::dfree(dstamps);
     if (hstamps) psx::hfree(hstamps);
@@ -1189,7 +1193,12 @@ SetRec null_rec(const psx_engine* e, double count);
 int eval_generic_staged(psx_engine* e, int stride, size_t nsets, bool accumulate, double* scores, double* kernel_ms,
                         bool user = false) {
     if (nsets == 0) return 0;
-    if (stride > PSX_KMAX) return fail(PSX_ERANGE, "union set larger than PSX_KMAX");
+    if (stride > PSX_KWIDE) return fail(PSX_ERANGE, "union set larger than PSX_KWIDE");
+    const bool wide = stride > PSX_KMAX;  // rows of 7 .. 10 entries: the wide evaluator (psx_wide.hip)
+    if (wide && !e->wtrace && std::getenv("PSX_WIDE_TRACE")) {
+        HIPCHK(psx::hmalloc(reinterpret_cast<void**>(&e->wtrace), 4 * sizeof(unsigned long long)));
+        std::memset(e->wtrace, 0, 4 * sizeof(unsigned long long));
+    }
     int rc;
     const size_t n_sets = nsets * stride;
     const bool chunked = accumulate && psx::batch_merge_chunks((long)nsets, stride) <= kBatchChunks && e->U <= 131072;
@@ -1221,7 +1230,16 @@ int eval_generic_staged(psx_engine* e, int stride, size_t nsets, bool accumulate
     unsigned long long* const bclk = clocks ? e->hbclk : nullptr;
     if (bclk) bclk[0] = bclk[1] = 0;
     if (kernel_ms && !clocks) HIPCHK(hipEventRecord(e->ev[2], e->stream));
-    if (user)  // (rows of at most 5 members: the 5-member instance, fewer live registers)
+    if (wide) {
+        const int wrc =
+            user ? psx::launch_eval_wide_batch(e->wp, e->dgen, e->dgen, stride, nsets, null_rec(e, 1.0), e->L0, badv,
+                                               dbad, reinterpret_cast<unsigned long long*>(e->hscore + nsets),
+                                               e->dsrec, e->dmrec, scores ? e->hscore : nullptr, bclk, e->wtrace,
+                                               e->stream)
+                 : psx::launch_eval_wide_sets(e->wp, e->dgen, stride, nsets, e->dsrec, e->dmrec,
+                                              scores ? e->dscore : nullptr, nullptr, e->wtrace, e->stream);
+        if (wrc) return fail(PSX_EHIP, "wide-set evaluation launch failed");
+    } else if (user)  // (rows of at most 5 members: the 5-member instance, fewer live registers)
         hipLaunchKernelGGL(stride <= 5 ? k_eval_batch5 : k_eval_batch, dim3((unsigned)nsets), dim3(64), 0,
                            e->stream, e->dp, e->dgen, e->dgen, stride, null_rec(e, 1.0), e->L0, badv, dbad,
                            reinterpret_cast<unsigned long long*>(e->hscore + nsets), e->dsrec, e->dmrec,
@@ -1269,6 +1287,10 @@ int eval_generic_staged(psx_engine* e, int stride, size_t nsets, bool accumulate
         return fail(PSX_EINVAL, "sets must be ascending union indices");
     if (scores)
         for (size_t i = 0; i < nsets; i++) scores[i] = e->K + e->hscore[i];
+    if (wide && e->wtrace && e->wtrace[2] > e->wtrace[0])
+        fprintf(stderr, "psx-wide-trace {\"stride\": %d, \"factor_us\": %.2f, \"butterfly_us\": %.2f}\n", stride,
+                1e3 * (double)(e->wtrace[1] - e->wtrace[0]) / (double)e->wclk_khz,
+                1e3 * (double)(e->wtrace[2] - e->wtrace[1]) / (double)e->wclk_khz);
     if (clocks) {
         const unsigned long long t0 = bclk[0], t1 = bclk[1];
         *kernel_ms += t1 > t0 ? (double)(t1 - t0) / (double)e->wclk_khz : 0.0;
@@ -1341,7 +1363,8 @@ int run_level_generic(psx_engine* e, int k, double* kms) {
     uint64_t lo = total * (uint64_t)e->rank / e->world;
     uint64_t hi = total * (uint64_t)(e->rank + 1) / e->world;
     if (lo >= hi) return 0;
-    const uint64_t CH = 1u << 20;
+    // (wide levels: fewer sets per chunk, the record buffers as large as at k = 6)
+    const uint64_t CH = k > PSX_KMAX ? ((uint64_t)PSX_KMAX << 20) / (uint64_t)k : 1u << 20;
     std::vector<int> c(k);
     unrank_lex(lo, e->U, k, c.data());
     uint64_t r = lo;
@@ -1453,8 +1476,14 @@ int enqueue_generic_level(psx_engine* e, int k) {
     g.ran = false;
     if (g.nsets == 0) return 0;
     HIPCHK(hipEventRecord(g.ev[0], e->stream));
-    hipLaunchKernelGGL(k_eval_sets, dim3((unsigned)g.nsets), dim3(64), 0, e->stream, e->dp, g.d_sets, k,
-                       (const int*)nullptr, g.d_srec, g.d_mrec, (double*)nullptr);
+    if (k > PSX_KMAX) {
+        if (psx::launch_eval_wide_sets(e->wp, g.d_sets, k, g.nsets, g.d_srec, g.d_mrec, nullptr, nullptr, nullptr,
+                                       e->stream))
+            return fail(PSX_EHIP, "wide-set evaluation launch failed");
+    } else {
+        hipLaunchKernelGGL(k_eval_sets, dim3((unsigned)g.nsets), dim3(64), 0, e->stream, e->dp, g.d_sets, k,
+                           (const int*)nullptr, g.d_srec, g.d_mrec, (double*)nullptr);
+    }
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(g.ev[1], e->stream));
     if (psx::launch_merge_members(g.d_mrec, g.d_csr, g.d_csr + g.ptr_len, g.d_csr + g.ptr_len + g.idx_len,
@@ -1848,7 +1877,7 @@ int create_impl(const psx_problem* p, const psx_ld_problem* ld, int device, psx_
     *out = nullptr;
     auto tc0 = std::chrono::steady_clock::now();
     if (!p || p->n_studies != 2) return fail(PSX_EINVAL, "only two studies are supported (postcal.cpp:20-23)");
-    if (p->max_causal < 0 || p->max_causal > PSX_KMAX) return fail(PSX_ERANGE, "max_causal outside [0, 6]");
+    if (p->max_causal < 0 || p->max_causal > PSX_KWIDE) return fail(PSX_ERANGE, "max_causal outside [0, 10]");
     if (p->n_union <= 0 || p->m[0] <= 0 || p->m[1] <= 0) return fail(PSX_EINVAL, "empty problem");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
@@ -2101,6 +2130,19 @@ int create_impl(const psx_problem* p, const psx_ld_problem* ld, int device, psx_
         dp.y[s] = e->dy[s];
     }
     dp.pres = e->dpres;
+    // the wide evaluator's view: the same pointers, the prior as per-member factors for k <= PSX_KWIDE
+    psx::WideProb& wp = e->wp;
+    std::memset(&wp, 0, sizeof(wp));
+    wp.U = dp.U;
+    wp.ldg = dp.ldg;
+    for (int s = 0; s < 2; s++) {
+        wp.G[s] = dp.G[s];
+        wp.Ad[s] = dp.Ad[s];
+        wp.y[s] = dp.y[s];
+        wp.dval[s] = dp.dval[s];
+    }
+    wp.pres = dp.pres;
+    psx::wide_prior(wp, e->U, p->gamma, p->sharing_param);
     if (hipMemsetAsync(e->dacc, 0, sizeof(Acc5) * ((size_t)e->ldg + 3), e->stream) != hipSuccess)
         return bail(fail(PSX_EHIP, "memset"));
     if (write_tag(e)) return bail(PSX_EHIP);
@@ -2200,6 +2242,8 @@ int psx_warmup_for(int device, int32_t max_causal, int32_t configs_file) {
         return fail(PSX_EHIP, "warm-up: sweep device code did not load");
     t[4] = now();
     if (max_causal >= 3 && psx::warm_module_sweep3()) return fail(PSX_EHIP, "warm-up: k = 3 device code did not load");
+    if (max_causal > PSX_KMAX && psx::warm_module_wide())
+        return fail(PSX_EHIP, "warm-up: wide-set device code did not load");
     t[5] = now();
     if (configs_file && psx::warm_module_configs()) return fail(PSX_EHIP, "warm-up: configs device code did not load");
     t[6] = now();
@@ -2454,7 +2498,7 @@ int psx_eval_union_batch(psx_engine* e, const int32_t* sets, int32_t stride, int
     HIPCHK(hipSetDevice(e->dev));
     e->stat_fresh = false;  // status changes: psx_sync reads it out again
     const auto t0 = std::chrono::steady_clock::now();
-    if (stride < 1 || stride > PSX_KMAX) return fail(PSX_ERANGE, "stride outside [1, 6]");
+    if (stride < 1 || stride > PSX_KWIDE) return fail(PSX_ERANGE, "stride outside [1, 10]");
     if (n_sets < 0 || (n_sets > 0 && !sets)) return fail(PSX_EINVAL, "bad set batch");
     // Rows go to the device as given (one pinned copy per slice); k_eval_batch
     // validates and compacts them and evaluates the null rows.  Slices of at
