@@ -224,8 +224,22 @@ int psx_run_configs(psx_engine *e, const int16_t *rows, int64_t n_rows, int32_t 
 /* PostCal::sss_computeTotalLikelihood (sss_postcal.cpp:102-380): stochastic
  * shotgun search, host random walk (mt19937(12345)) + GPU neighbour batches.
  * The walk (set keys, iteration state, neighbour kernels) is sized for at most
- * 6 causal SNPs: PSX_ERANGE on a handle created with max_causal 7..10. */
+ * 6 causal SNPs: PSX_ERANGE on a handle created with max_causal 7..10.  That
+ * contract is unchanged (ABI 4, and a test of the suite holds it); the walk of
+ * 7..10 is reached through psx_run_sss_wide below. */
 int psx_run_sss(psx_engine *e, int32_t *iterations_out);
+
+/* sss_computeTotalLikelihood for a handle of max_causal 0..10.  max_causal <= 6:
+ * exactly psx_run_sss (same kernels, bitwise the same accumulators).  7..10: the
+ * wide walk, one rank: every iteration evaluates the current configuration and
+ * its neighbourhood on the wide-set evaluator (one 256-thread workgroup per
+ * set, a set map of 48-byte entries for up to 10 members).  Same walk semantics
+ * as psx_run_sss (mt19937(12345), the reference's neighbour order, draws and
+ * stop tests).  A separate entry only because psx_run_sss's PSX_ERANGE for
+ * 7..10 is held by the suite: the two are to be folded into psx_run_sss once
+ * that test is retired.  The sharded and multi-device walks
+ * (psx_run_sss_sharded*, psx_multi_run_sss) keep PSX_ERANGE for 7..10. */
+int psx_run_sss_wide(psx_engine *e, int32_t *iterations_out);
 
 /* All-gather callback of the sharded SSS walk: gather `bytes` host bytes from
  * every rank into recv (world * bytes, rank order).  Returns 0 on success.  The

@@ -417,6 +417,14 @@ int main(int argc, char* argv[]) {
         devices.push_back(0);
     }
     if (devices.empty()) devices.push_back(0);
+    // -q 1 with -c 7..10: the wide SSS walk (psx_run_sss_wide), which runs on one handle
+    const bool sss_wide = sss_flag == 1 && totalCausalSNP > 6;
+    if (sss_wide && ds) {
+        fprintf(stderr, "PIPSORT: -q 1 -c %d runs on one device (%d); PSX_DEVICES is not used\n", totalCausalSNP,
+                (int)devices[0]);
+        devices.resize(1);
+        defer_devices = false;
+    }
     const int device = devices[0];
     g_multi = devices.size() > 1;
     // one locus per process: one stream (hardware queue) per device for the
@@ -426,7 +434,8 @@ int main(int argc, char* argv[]) {
     psx_single_queue(sq ? atoi(sq) : 1);
     // the HIP runtime / contexts come up on a second thread while the inputs
     // are parsed (errors, if any, surface again at psx_create*)
-    const int warm_c = sss_flag == 1 ? 0 : totalCausalSNP;  // SSS batches run the generic set kernel
+    // (SSS batches run the generic set kernel; the wide walk its own code object, loaded for -c > 6)
+    const int warm_c = sss_flag == 1 && !sss_wide ? 0 : totalCausalSNP;
     const int warm_b = configsFile != "";
     std::thread warm([devices, warm_c, warm_b] {
         g_ph.rt0 = epoch_ms();
@@ -604,7 +613,8 @@ int main(int argc, char* argv[]) {
         if (p) munmap(p, sz);
     } else if (sss_flag == 1) {
         int32_t iters = 0;
-        rc = g_multi ? psx_multi_run_sss(multi, &iters) : psx_run_sss(eng, &iters);
+        rc = sss_wide ? psx_run_sss_wide(eng, &iters)
+             : g_multi ? psx_multi_run_sss(multi, &iters) : psx_run_sss(eng, &iters);
         printf("sss iterations = %d\n", iters);
     } else {
         rc = g_multi ? psx_multi_run_exhaustive(multi) : psx_run_exhaustive(eng);

@@ -30,6 +30,7 @@
 #include "psx_sweep_dev.h"
 #include "psx_mem.h"
 #include "psx_wave.h"
+#include "psx_sss_wide.h"
 #include "psx_wide.h"
 
 extern "C" __device__ __attribute__((const)) double __ockl_wfred_min_f64(double);
@@ -2242,7 +2243,8 @@ int psx_warmup_for(int device, int32_t max_causal, int32_t configs_file) {
         return fail(PSX_EHIP, "warm-up: sweep device code did not load");
     t[4] = now();
     if (max_causal >= 3 && psx::warm_module_sweep3()) return fail(PSX_EHIP, "warm-up: k = 3 device code did not load");
-    if (max_causal > PSX_KMAX && psx::warm_module_wide())
+    // (sets of 7 .. 10 members: the wide evaluator and the wide SSS walk, small code objects both)
+    if (max_causal > PSX_KMAX && (psx::warm_module_wide() || psx::warm_module_sss_wide()))
         return fail(PSX_EHIP, "warm-up: wide-set device code did not load");
     t[5] = now();
     if (configs_file && psx::warm_module_configs()) return fail(PSX_EHIP, "warm-up: configs device code did not load");
@@ -3068,8 +3070,16 @@ struct SssDev {
     double* hnorm = nullptr;  // pinned host: every rank's normaliser (m, s) (device exchange)
     int cap_hnorm = 0;
     unsigned int seq = 0;     // the last iteration tag of the mark words (never 0)
+    // the wide walk (max_causal 7 .. 10, run_sss_wide): its own map and per-neighbour keys / host marks
+    psx::WideMapEntry* TW = nullptr;
+    size_t cap_w = 0, nmax_w = 0;
+    unsigned long long* keys = nullptr;  // per neighbour: its packed set (four words)
+    int* hmk = nullptr;                  // pinned host: per neighbour, its mark
     ~SssDev() {
         psx::dfree(T);
+        psx::dfree(TW);
+        psx::dfree(keys);
+        if (hmk) psx::hfree(hmk);
         psx::dfree(rows);
         psx::dfree(mark);
         psx::dfree(cnt);
@@ -3090,8 +3100,9 @@ struct SssDev {
 void sss_release(SssDev* d) { delete d; }
 
 // the walk's workspace for up to nmax items per iteration (grown, never shrunk;
-// the map is cleared for every walk)
-int sss_workspace(psx_engine* e, size_t nmax, int world, hipStream_t s) {
+// the map is cleared for every walk); wide: the wide walk's map and keys
+// instead of the narrow map
+int sss_workspace(psx_engine* e, size_t nmax, int world, hipStream_t s, bool wide = false) {
     if (!e->sss) e->sss = new SssDev();
     SssDev& D = *e->sss;
     if (!D.cnt) {
@@ -3131,6 +3142,28 @@ int sss_workspace(psx_engine* e, size_t nmax, int world, hipStream_t s) {
     }
     size_t cap = 1 << 16;
     while (cap < 4 * nmax) cap <<= 1;
+    if (wide) {
+        if (D.nmax_w < nmax) {
+            psx::dfree(D.keys);
+            if (D.hmk) psx::hfree(D.hmk);
+            D.keys = nullptr;
+            D.hmk = nullptr;
+            D.nmax_w = 0;
+            HIPCHK(psx::dmalloc(&D.keys, nmax * 4 * sizeof(unsigned long long)));
+            HIPCHK(psx::hmalloc(&D.hmk, nmax * sizeof(int)));
+            D.nmax_w = nmax;
+        }
+        if (D.cap_w < cap) {
+            psx::dfree(D.TW);
+            D.TW = nullptr;
+            D.cap_w = 0;
+            HIPCHK(psx::dmalloc(&D.TW, cap * sizeof(psx::WideMapEntry)));
+            D.cap_w = cap;
+        }
+        HIPCHK(hipMemsetAsync(D.TW, 0, D.cap_w * sizeof(psx::WideMapEntry), s));
+        D.used = 0;
+        return 0;
+    }
     if (D.cap < cap) {
         psx::dfree(D.T);
         D.T = nullptr;
@@ -3140,6 +3173,58 @@ int sss_workspace(psx_engine* e, size_t nmax, int world, hipStream_t s) {
     HIPCHK(hipMemsetAsync(D.T, 0, D.cap * sizeof(MapEntry), s));
     D.used = 0;
     return 0;
+}
+
+// The next configuration: one neighbour drawn from every neighbour's score
+// lk[0 .. n_nbd) (swap ++ minus ++ plus) with the reference's draws in the
+// reference's order (sss_postcal.cpp:296-343), put in cur[0 .. k) (ascending).
+void sss_sample_next(const double* lk, int num_zero, int num_minus, int num_plus, std::mt19937& gen,
+                     std::vector<double>& pr, int* cur, int& k) {
+    const int n_nbd = num_zero + num_minus + num_plus;
+    double wz = 0, wm = 0, wp = 0;
+    size_t zs = n_nbd, ms = n_nbd, ps = n_nbd;
+    // each group: discrete_distribution(exp(lk - max))(gen) and the weights'
+    // sum (accumulate), the draw restated without the distribution's vectors
+    // (psx_sample.h: bit-identical partial sums, the same index)
+    auto group = [&](int b, int en, double& wsum, size_t& smp) {
+        pr.resize((size_t)(en - b));
+        double mx = *std::max_element(lk + b, lk + en);
+        // (slicing these exps over spinning host threads measured slower: the
+        // serial loop takes ~5 us at 1,000 neighbours, profiles/archive/r03v_sss_threads.txt)
+        double s = 0.0;
+        for (int ii = b; ii < en; ii++) s += (pr[ii - b] = std::exp(lk[ii] - mx));
+        smp = psx::discrete_draw(pr.data(), pr.size(), s, gen);
+        wsum = s;
+    };
+    if (num_zero != 0) group(0, num_zero, wz, zs);                               // :296-306
+    if (num_minus != 0) group(num_zero, num_zero + num_minus, wm, ms);           // :307-317
+    if (num_plus != 0) group(num_zero + num_minus, n_nbd, wp, ps);               // :318-328
+    const double w3[3] = {wz, wm, wp};                                           // :330-343
+    size_t idx = psx::discrete_draw(w3, 3, (0.0 + wz + wm) + wp, gen), fin = 0;
+    switch (idx) {
+        case 0: fin = zs; break;
+        case 1: fin = ms + num_zero; break;
+        case 2: fin = ps + num_zero + num_minus; break;
+    }
+    // the chosen neighbour becomes the current configuration (host copy of nbd_row)
+    const int i = (int)fin;
+    int x = -1, skip = -1, n;
+    if (i < num_zero) { skip = i % k; x = i / k; n = k; }
+    else if (i < num_zero + num_minus) { skip = i - num_zero; n = k - 1; }
+    else { x = i - num_zero - num_minus; n = k + 1; }
+    if (x >= 0)
+        for (int j = 0; j < k; j++)
+            if (cur[j] <= x) x++;
+    int nxt[PSX_KWIDE], m = 0;
+    bool put = x < 0;
+    for (int j = 0; j < k; j++) {
+        if (j == skip) continue;
+        if (!put && x < cur[j]) { nxt[m++] = x; put = true; }
+        nxt[m++] = cur[j];
+    }
+    if (!put) nxt[m++] = x;
+    std::copy(nxt, nxt + n, cur);
+    k = n;
 }
 
 int run_sss(psx_engine* e, psx_allgather_fn allgather, psx_allgather_dev_fn dgather, void* ctx,
@@ -3373,53 +3458,7 @@ int run_sss(psx_engine* e, psx_allgather_fn allgather, psx_allgather_dev_fn dgat
         if (unseen == 0) break;                                                          // :260-263
         // (one rank: the sampling below runs first and is dropped when the stop
         // test of sss_postcal.cpp:265-270 ends the walk — it only advances gen)
-        const double* lk = D.lk;
-        double wz = 0, wm = 0, wp = 0;
-        size_t zs = n_nbd, ms = n_nbd, ps = n_nbd;
-        // each group: discrete_distribution(exp(lk - max))(gen) and the weights'
-        // sum (accumulate), the draw restated without the distribution's vectors
-        // (psx_sample.h: bit-identical partial sums, the same index)
-        auto group = [&](int b, int en, double& wsum, size_t& smp) {
-            pr.resize((size_t)(en - b));
-            double mx = *std::max_element(lk + b, lk + en);
-            // (slicing these exps over spinning host threads measured slower: the
-            // serial loop takes ~5 us at 1,000 neighbours, profiles/archive/r03v_sss_threads.txt)
-            double s = 0.0;
-            for (int ii = b; ii < en; ii++) s += (pr[ii - b] = std::exp(lk[ii] - mx));
-            smp = psx::discrete_draw(pr.data(), pr.size(), s, gen);
-            wsum = s;
-        };
-        if (it.num_zero != 0) group(0, it.num_zero, wz, zs);                               // :296-306
-        if (it.num_minus != 0) group(it.num_zero, it.num_zero + it.num_minus, wm, ms);     // :307-317
-        if (it.num_plus != 0) group(it.num_zero + it.num_minus, n_nbd, wp, ps);            // :318-328
-        const double w3[3] = {wz, wm, wp};                                                 // :330-343
-        size_t idx = psx::discrete_draw(w3, 3, (0.0 + wz + wm) + wp, gen), fin = 0;
-        switch (idx) {
-            case 0: fin = zs; break;
-            case 1: fin = ms + it.num_zero; break;
-            case 2: fin = ps + it.num_zero + it.num_minus; break;
-        }
-        // the chosen neighbour becomes the current configuration (host copy of nbd_row)
-        {
-            const int i = (int)fin;
-            int x = -1, skip = -1, n;
-            if (i < it.num_zero) { skip = i % k; x = i / k; n = k; }
-            else if (i < it.num_zero + it.num_minus) { skip = i - it.num_zero; n = k - 1; }
-            else { x = i - it.num_zero - it.num_minus; n = k + 1; }
-            if (x >= 0)
-                for (int j = 0; j < k; j++)
-                    if (cur[j] <= x) x++;
-            int nxt[PSX_KMAX], m = 0;
-            bool put = x < 0;
-            for (int j = 0; j < k; j++) {
-                if (j == skip) continue;
-                if (!put && x < cur[j]) { nxt[m++] = x; put = true; }
-                nxt[m++] = cur[j];
-            }
-            if (!put) nxt[m++] = x;
-            std::copy(nxt, nxt + n, cur);
-            k = n;
-        }
+        sss_sample_next(D.lk, it.num_zero, it.num_minus, it.num_plus, gen, pr, cur, k);
         tick(2, tp);
         if (world == 1 && iter >= 99) {  // the normaliser of this iteration (k_sss_post)
             HIPCHK(hipStreamSynchronize(e->stream));
@@ -3458,10 +3497,133 @@ int run_sss(psx_engine* e, psx_allgather_fn allgather, psx_allgather_dev_fn dgat
     e->timing.configs = (uint64_t)(s.npat + 0.5);
     return 0;
 }
+
+// The walk for max_causal 7 .. PSX_KWIDE, one rank: run_sss's iteration (the
+// same geometry, draws and stop tests) around k_sss_eval_wide / k_sss_post_wide
+// (psx_sss_wide.hip) and the wide set map.  The host waits on the eval's stop
+// event, reads every neighbour's weight and mark from pinned memory and samples
+// the next configuration while the post runs.
+int run_sss_wide(psx_engine* e, int32_t* iterations_out) {
+    HIPCHK(hipSetDevice(e->dev));
+    e->stat_fresh = false;
+    int rc;
+    if ((rc = reset_acc(e))) return rc;
+    std::memset(&e->timing, 0, sizeof(e->timing));
+    const int U = e->U, C = e->maxc;
+    if (C <= PSX_KMAX || C > PSX_KWIDE) return fail(PSX_ERANGE, "wide SSS walk: max_causal outside [7, 10]");
+    if (U > kKeyMaxU) return fail(PSX_ERANGE, "SSS: more union SNPs than the set key holds");
+    const int stride = C;
+    const size_t nmax = (size_t)C * U + C + U + 2;  // as run_sss
+    if ((rc = sss_workspace(e, nmax, 1, e->stream, true))) return rc;
+    SssDev& D = *e->sss;
+    if ((rc = ensure(e->dsrec, e->cap_srec, nmax))) return rc;
+    if ((rc = ensure(e->dmrec, e->cap_mrec, nmax * stride))) return rc;
+    if ((rc = ensure(e->dscore, e->cap_score, nmax))) return rc;
+    const SetRec null1 = null_rec(e, 1.0);
+    std::mt19937 gen(12345);
+    int cur[PSX_KWIDE] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, k = 0;  // the current configuration, ascending
+    double old_sum = 0, kms = 0;
+    int iter, ksamples = 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<double> pr;
+    size_t items = 0;  // PSX_SSS_PROFILE: items launched (D.used: sets evaluated)
+    for (iter = 0; iter < 1000; iter++) {
+        psx::SssWideIter it;
+        for (int j = 0; j < PSX_KWIDE; j++) it.cur[j] = j < k ? cur[j] : -1;
+        it.k = k;
+        it.U = U;
+        it.stride = stride;
+        it.num_zero = (U - k) * k;
+        it.num_minus = k;
+        it.num_plus = k < C ? U - k : 0;
+        it.n_nbd = it.num_zero + it.num_minus + it.num_plus;
+        it.null_score = e->K + e->L0;
+        const int n_nbd = it.n_nbd;
+        items += (size_t)n_nbd + 1;
+        // the map stays at load <= 1/2 (every neighbour may be new)
+        if (2 * (D.used + (size_t)n_nbd + 1) > D.cap_w) {
+            size_t nc = D.cap_w;
+            while (2 * (D.used + (size_t)n_nbd + 1) > nc) nc <<= 1;
+            psx::WideMapEntry* nt = nullptr;
+            HIPCHK(psx::dmalloc(&nt, nc * sizeof(psx::WideMapEntry)));
+            HIPCHK(hipMemsetAsync(nt, 0, nc * sizeof(psx::WideMapEntry), e->stream));
+            if (psx::launch_wide_map_rehash(D.TW, D.cap_w, nt, (unsigned long long)(nc - 1), e->stream)) {
+                psx::dfree(nt);
+                return fail(PSX_EHIP, "wide SSS map rehash launch failed");
+            }
+            HIPCHK(hipStreamSynchronize(e->stream));
+            psx::dfree(D.TW);
+            D.TW = nt;
+            D.cap_w = nc;
+        }
+        const unsigned long long mask = D.cap_w - 1;
+        // the event ring of run_sss: the eval time sampled on every kEvEvery-th
+        // iteration, the stop event (the host's wait) on every one
+        hipEvent_t* evp = D.ev + 2 * (iter % SssDev::kRingE);
+        const bool timed = iter % SssDev::kEvEvery == 0;
+        if (iter >= SssDev::kRingE && (iter - SssDev::kRingE) % SssDev::kEvEvery == 0) {
+            float ms = 0;
+            HIPCHK(hipEventElapsedTime(&ms, evp[0], evp[1]));
+            kms += ms;
+            ksamples++;
+        }
+        if (timed) HIPCHK(hipEventRecord(evp[0], e->stream));
+        if (psx::launch_sss_eval_wide(e->wp, it, D.TW, mask, D.mark, D.cnt, D.keys, D.lk, D.hmk, e->dsrec, e->dmrec,
+                                      e->dscore, e->stream))
+            return fail(PSX_EHIP, "wide SSS evaluation launch failed");
+        HIPCHK(hipEventRecord(evp[1], e->stream));
+        if (psx::launch_sss_post_wide(it, D.mark, D.cnt, D.keys, e->dmrec, e->dsrec, e->dscore, null1, e->dacc,
+                                      e->dsacc, D.shost, D.hcnt, D.TW, mask, e->stream))
+            return fail(PSX_EHIP, "wide SSS post launch failed");
+        HIPCHK(hipEventSynchronize(evp[1]));
+        int unseen = 0;
+        for (int i = 0; i < n_nbd; i++) unseen += D.hmk[i] != -1;
+        D.used += (size_t)unseen;
+        if (unseen == 0) break;                                                          // :260-263
+        // (the sampling runs first and is dropped when the stop test of
+        // sss_postcal.cpp:265-270 ends the walk — it only advances gen)
+        sss_sample_next(D.lk, it.num_zero, it.num_minus, it.num_plus, gen, pr, cur, k);
+        double sss_sum = 0.0;
+        if (iter >= 99) {  // the normaliser of this iteration (k_sss_post_wide)
+            HIPCHK(hipStreamSynchronize(e->stream));
+            sss_sum = logval(e, D.shost->m, D.shost->tot);
+        }
+        if (iter >= 100 && (1 - std::exp(old_sum - sss_sum)) <= 0.001) break;            // :265-270
+        old_sum = sss_sum;
+    }
+    HIPCHK(hipStreamSynchronize(e->stream));  // the last iteration's post
+    const auto t1 = std::chrono::steady_clock::now();
+    {  // the evals still in the event ring
+        const int ran = std::min(iter + 1, 1000);
+        for (int q = std::max(0, ran - SssDev::kRingE); q < ran; q++) {
+            if (q % SssDev::kEvEvery) continue;
+            float ms = 0;
+            HIPCHK(hipEventElapsedTime(&ms, D.ev[2 * (q % SssDev::kRingE)], D.ev[2 * (q % SssDev::kRingE) + 1]));
+            kms += ms;
+            ksamples++;
+        }
+        if (ksamples) kms *= (double)ran / ksamples;  // the sampled evals' mean, over every iteration
+    }
+    if (std::getenv("PSX_SSS_PROFILE"))
+        fprintf(stderr, "[psx sss wide] %d iterations, %zu items, %zu unseen neighbours, eval %.3f ms\n", iter, items,
+                D.used, kms);
+    if (iterations_out) *iterations_out = iter;
+    e->timing.sweep_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    e->timing.kernel_ms = kms;
+    SetRec s;
+    HIPCHK(hipMemcpy(&s, e->dsacc, sizeof(SetRec), hipMemcpyDeviceToHost));
+    e->timing.configs = (uint64_t)(s.npat + 0.5);
+    return 0;
+}
 }  // namespace
 
 int psx_run_sss(psx_engine* e, int32_t* iterations_out) {
     return run_sss(e, nullptr, nullptr, nullptr, iterations_out);
+}
+
+int psx_run_sss_wide(psx_engine* e, int32_t* iterations_out) {
+    return e->maxc <= PSX_KMAX ? run_sss(e, nullptr, nullptr, nullptr, iterations_out)
+                               : run_sss_wide(e, iterations_out);
 }
 
 int psx_run_sss_sharded(psx_engine* e, psx_allgather_fn allgather, void* ctx, int32_t* iterations_out) {

@@ -32,7 +32,7 @@ PSX_EEXCHANGE = -7
 # Every symbol declared in include/pipsort_engine.h and include/pipsort_model.h
 EXPORTED = [
     "psx_abi_version", "psx_overlap_cus", "psx_last_error", "psx_device_count", "psx_pool_trim", "psx_pool_cached_bytes", "psx_warmup", "psx_warmup_for", "psx_single_queue", "psx_create", "psx_destroy",
-    "psx_set_shard", "psx_run_exhaustive", "psx_run_configs", "psx_run_sss",
+    "psx_set_shard", "psx_run_exhaustive", "psx_run_configs", "psx_run_sss", "psx_run_sss_wide",
     "psx_eval_union_batch", "psx_reset", "psx_get_accum", "psx_partials_bytes",
     "psx_export_partials", "psx_partials_device_ptr", "psx_merge_partials", "psx_get_timing", "psx_count_configs",
     "psx_fold_partials_host", "psx_plan_hash", "psx_plan_build_ms", "psx_plan_csr_selftest", "psx_shard_stats", "psx_plan_units_k3", "psx_set_stream",
@@ -179,6 +179,7 @@ def load_library(path: str = LIB_PATH):
         "psx_run_exhaustive": (c_int, [vp]),
         "psx_run_configs": (c_int, [vp, P(ctypes.c_int16), c_i64, c_i32]),
         "psx_run_sss": (c_int, [vp, P(c_i32)]),
+        "psx_run_sss_wide": (c_int, [vp, P(c_i32)]),
         "psx_eval_union_batch": (c_int, [vp, P(c_i32), c_i32, c_i32, c_int, P(dbl)]),
         "psx_reset": (c_int, [vp]),
         "psx_get_accum": (c_int, [vp, P(_Accum)]),
@@ -701,6 +702,13 @@ class PostCal:
         """sss_postcal.cpp:102 sss_computeTotalLikelihood; returns iterations."""
         it = ctypes.c_int32(0)
         _check(self.lib.psx_run_sss(self.h, ctypes.byref(it)))
+        return it.value
+
+    def run_sss_wide(self) -> int:
+        """The SSS walk for max_causal 0..10 (psx_run_sss_wide): run_sss itself up
+        to 6, the wide-set walk for 7..10; returns iterations."""
+        it = ctypes.c_int32(0)
+        _check(self.lib.psx_run_sss_wide(self.h, ctypes.byref(it)))
         return it.value
 
     def run_sss_sharded(self, allgather) -> int:
