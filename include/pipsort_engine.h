@@ -47,7 +47,8 @@ typedef struct {
     int32_t n_union;                /* unionSnpCount = rows of the snp map                       */
     const int32_t *union_to_local;  /* [n_studies][n_union] idx_to_snp_map, -1 = absent          */
     int32_t max_causal;             /* MAX_causal (-c), 0..10 (PSX_ERANGE otherwise); the SSS    */
-                                    /* walk and -b rows serve at most 6 causal union SNPs        */
+                                    /* walk of psx_run_sss serves at most 6 causal union SNPs;   */
+                                    /* -b rows name up to 10 on a handle of any max_causal       */
     const int32_t *sample_sizes;    /* [n_studies] (-n)                                          */
     double sharing_param;           /* -p */
     double gamma;                   /* -g */
@@ -218,7 +219,14 @@ int psx_run_exhaustive_async(psx_engine *e);
 int psx_sync(psx_engine *e, int32_t *exact_needed);
 
 /* PostCal::computeTotalLikelihoodGivenConfigs (postcal.cpp:400-714): rows of
- * int16 global SNP indices (-1 = none), [n_rows][n_groups] (the -b file). */
+ * int16 global SNP indices (-1 = none), [n_rows][n_groups] (the -b file).  A
+ * row names up to 10 distinct union SNPs (up to 10 causal per study, -1
+ * anywhere), on a handle of any max_causal; the first failing row in row order
+ * decides: PSX_EINVAL (index out of range), PSX_ERANGE (more than 10 union
+ * SNPs), PSX_EORDER (postcal.cpp:587-590).  A file whose rows all name <= 6
+ * union SNPs takes the narrow path (a lane per row); one with a row of 7..10 is
+ * counted again under the wide rules and takes the wide path as a whole (its
+ * factorisations dealt to the lanes by size). */
 int psx_run_configs(psx_engine *e, const int16_t *rows, int64_t n_rows, int32_t n_groups);
 
 /* PostCal::sss_computeTotalLikelihood (sss_postcal.cpp:102-380): stochastic

@@ -32,6 +32,12 @@
 //                the chunk partials in order (the one-block fold took 6 ms on
 //                4.8M rows)
 //
+// A file with a row of 7 .. PSX_KWIDE union SNPs (the first failing row of
+// k_cfg_count<PSX_KMAX> has code 2) is counted again as k_cfg_count<PSX_KWIDE>
+// and takes the wide path as a whole: k_cfg_eval_wide (below) for k_cfg_eval and
+// k_cfg_merge<PSX_KWIDE> for the member fold; everything else is shared.  A file
+// of rows of <= PSX_KMAX SNPs runs the launches it always ran.
+//
 // Every fold order is fixed by the row order and the launch shapes, so the
 // results are deterministic (and within rounding of the host pre-pass this
 // replaced).
@@ -68,11 +74,13 @@ struct CfgRow {
 };
 
 // postcal.cpp:441-590 for one row, as the host pass restated it: returns k
-// (0: null row), -1 an index outside [0, N), -2 more than PSX_KMAX union SNPs,
-// -3 the study-major walk failed (postcal.cpp:587-590).  locs: the sorted union
+// (0: null row), -1 an index outside [0, N), -2 more than KM union SNPs (KM =
+// PSX_KMAX on the narrow path, PSX_KWIDE on the wide one), -3 the study-major
+// walk failed (postcal.cpp:587-590).  locs: the sorted union
 // positions; b0 / b1: the members causal in study 0 / 1.  Register-only (every
 // array index is a compile-time constant after unrolling).
-__device__ int cfg_row(const int16_t* in, int ng, const CfgMaps& C, int (&locs)[PSX_KMAX], int& b0, int& b1) {
+template <int KM>
+__device__ int cfg_row(const int16_t* in, int ng, const CfgMaps& C, int (&locs)[KM], int& b0, int& b1) {
     int n = 0;
     bool over = false;
     for (int i = 0; i < ng; i++) {
@@ -83,21 +91,21 @@ __device__ int cfg_row(const int16_t* in, int ng, const CfgMaps& C, int (&locs)[
         bool dup = false;
         int p = 0;  // insertion position: members below u
 #pragma unroll
-        for (int q = 0; q < PSX_KMAX; q++)
+        for (int q = 0; q < KM; q++)
             if (q < n) {
                 dup |= locs[q] == u;
                 p += locs[q] < u;
             }
         if (dup) continue;
-        if (n == PSX_KMAX) {
+        if (n == KM) {
             over = true;
             continue;
         }
 #pragma unroll
-        for (int q = PSX_KMAX - 1; q > 0; q--)
+        for (int q = KM - 1; q > 0; q--)
             if (q > p && q <= n) locs[q] = locs[q - 1];
 #pragma unroll
-        for (int q = 0; q < PSX_KMAX; q++)
+        for (int q = 0; q < KM; q++)
             if (q == p) locs[q] = u;
         n++;
     }
@@ -112,7 +120,7 @@ __device__ int cfg_row(const int16_t* in, int ng, const CfgMaps& C, int (&locs)[
         const int offi = i ? C.m0 : 0;
         bool stop = false;
 #pragma unroll
-        for (int j = 0; j < PSX_KMAX; j++) {
+        for (int j = 0; j < KM; j++) {
             if (j >= n || stop) continue;
             const int loc = C.u2l[i * C.U + locs[j]];
             if (loc < 0) continue;
@@ -167,6 +175,7 @@ __device__ void block_exscan2(int a, int b, int& pa, int& pb, int& ta, int& tb) 
     __syncthreads();  // sa / sb are reused by the next call
 }
 
+template <int KM>
 __global__ __launch_bounds__(kRowsPerBlock) void k_cfg_count(const int16_t* __restrict__ rows, long n_rows, int ng,
                                                             CfgMaps C, long r0, long r1,
                                                             unsigned long long* __restrict__ status,
@@ -177,15 +186,15 @@ __global__ __launch_bounds__(kRowsPerBlock) void k_cfg_count(const int16_t* __re
         for (int u = threadIdx.x; u < C.U; u += kRowsPerBlock) sh_hist[u] = 0;
     __syncthreads();
     const long r = (long)blockIdx.x * kRowsPerBlock + threadIdx.x;
-    int locs[PSX_KMAX] = {0, 0, 0, 0, 0, 0}, b0 = 0, b1 = 0, code = 0;
+    int locs[KM] = {}, b0 = 0, b1 = 0, code = 0;
     if (r < n_rows) {
-        code = cfg_row(rows + r * ng, ng, C, locs, b0, b1);
+        code = cfg_row<KM>(rows + r * ng, ng, C, locs, b0, b1);
         if (code < 0) atomicMin(&status[0], ((unsigned long long)r << 3) | (unsigned long long)(-code));
     }
     const bool mine = r >= r0 && r < r1;
     const int k = (mine && code > 0) ? code : 0;
 #pragma unroll
-    for (int j = 0; j < PSX_KMAX; j++)
+    for (int j = 0; j < KM; j++)
         if (j < k) {
             if (lds_hist) atomicAdd(&sh_hist[locs[j]], 1);
             else atomicAdd(&hist[locs[j]], 1);
@@ -261,7 +270,7 @@ __global__ __launch_bounds__(kRowsPerBlock) void k_cfg_eval(const int16_t* __res
     const long r = (long)blockIdx.x * kRowsPerBlock + threadIdx.x;
     int mem[KM] = {0, 0, 0, 0, 0, 0}, c0 = 0, c1 = 0, k = 0;
     if (r >= r0 && r < r1) {
-        const int code = cfg_row(rows + r * ng, ng, C, mem, c0, c1);
+        const int code = cfg_row<KM>(rows + r * ng, ng, C, mem, c0, c1);
         k = code > 0 ? code : 0;  // failing rows were rejected before this launch
     }
     int ps, pr, ts, tr;
@@ -312,7 +321,7 @@ __global__ __launch_bounds__(kRowsPerBlock) void k_cfg_eval(const int16_t* __res
     }
     srec[si] = rr;
     rrec[si] = row;
-    masks[si] = c0 | (c1 << 8);
+    masks[si] = c0 | (c1 << 16);
 #pragma unroll
     for (int j = 0; j < KM; j++)
         if (j < k) {
@@ -321,14 +330,223 @@ __global__ __launch_bounds__(kRowsPerBlock) void k_cfg_eval(const int16_t* __res
         }
 }
 
+// ---- The wide path: files with a row of 7 .. PSX_KWIDE union SNPs ----
+//
+// A row costs its two forced factorisations, ~t^3 / 3 each for t = 0 .. 10
+// causal members of the study, and a product file mixes every size in every
+// wave: with a lane per row each wave would run at the cost of its largest
+// member.  So a block's 512 factorisations (256 rows x 2 studies) are dealt to
+// the lanes by size through LDS:
+//   walk     thread r walks row r and writes two task descriptors (the study's
+//            t causal union indices, 16 bits each); a counting sort on t (11
+//            bins: LDS histogram, prefix) orders the 512 tasks by size
+//   factor   thread x takes sorted tasks x and 511 - x, one after the other in
+//            the same registers: a wave's 64 tasks have (nearly) one size, and
+//            a small batch is paired with a large one so that the four waves
+//            of the block finish together.  The 10 x 10 LDL^T is unrolled
+//            with static register indices; the wave's largest t cuts the row
+//            steps off as a uniform branch.  (n, mu, f) go back to LDS at the
+//            task's own (row, study) slot
+//   combine  thread r reads its two results and writes what k_cfg_eval writes
+constexpr int KW = PSX_KWIDE;
+constexpr int kTasks = 2 * kRowsPerBlock;
+
+// what the wide evaluation reads of the device problem: CfgProb with the prior
+// tables in device memory (2 KB for k <= 10: not kernel arguments)
+struct CfgProbWide {
+    const double* G[2];
+    const double* Ad[2];
+    const double* y[2];
+    const unsigned char* pres;
+    const CfgPrior* prior;
+    int ldg;
+    double dval[2];
+};
+
+struct CfgWideShm {
+    unsigned short idx[kTasks][KW];  // task 2 * row + study: its t union indices, then 0 (a safe gather)
+    unsigned short order[kTasks];    // the tasks by ascending t
+    unsigned char t[kTasks];
+    double mu[kTasks], f[kTasks];    // the results, at the task's own slot
+    int n[kTasks];
+    int hist[KW + 1];
+};
+
+// ldlt_terms (psx_math.h) for t <= 10 members, register-only: the same
+// left-looking order, one division per pivot.  L overwrites the gathered lower
+// triangle in place.  tmax (wave-uniform, >= t) bounds the row steps; a lane
+// past its own t works on entry 0's operands and keeps q and P as they are.
+// All t (t - 1) / 2 + 2 t gathers are issued before the arithmetic.
+__device__ __forceinline__ void ldlt_wide(const double* __restrict__ G, int ldg, const double* __restrict__ Ad,
+                                          const double* __restrict__ y, double dval, const int (&ix)[KW], int t,
+                                          int tmax, double& q, double& P) {
+    double L[KW * (KW - 1) / 2], D[KW], Rd[KW], w[KW];
+#pragma unroll
+    for (int i = 0; i < KW; i++)
+        if (i < tmax) {
+            const double* Gi = G + (size_t)ix[i] * ldg;
+#pragma unroll
+            for (int j = 0; j < i; j++) L[i * (i - 1) / 2 + j] = Gi[ix[j]];
+            D[i] = Ad[ix[i]];
+            w[i] = y[ix[i]];
+        }
+    q = 0.0;
+    P = 1.0;
+#pragma unroll
+    for (int i = 0; i < KW; i++)
+        if (i < tmax) {
+            double* Li = L + i * (i - 1) / 2;
+#pragma unroll
+            for (int j = 0; j < i; j++) {
+                const double* Lj = L + j * (j - 1) / 2;
+                double acc = Li[j];
+#pragma unroll
+                for (int m = 0; m < j; m++) acc -= Li[m] * Lj[m] * D[m];
+                Li[j] = acc * Rd[j];
+            }
+            double di = D[i], wi = w[i];
+#pragma unroll
+            for (int m = 0; m < i; m++) {
+                di -= Li[m] * Li[m] * D[m];
+                wi -= Li[m] * w[m];
+            }
+            D[i] = di;
+            Rd[i] = 1.0 / di;
+            w[i] = wi;
+            if (i < t) {
+                q += wi * wi * Rd[i];
+                P *= dval * di;
+            }
+        }
+}
+
+__global__ __launch_bounds__(kRowsPerBlock) void k_cfg_eval_wide(const int16_t* __restrict__ rows, int ng, CfgMaps C,
+                                                                long r0, long r1, CfgProbWide P,
+                                                                const int* __restrict__ blk, int nblk,
+                                                                SetRec* __restrict__ srec, CfgRow* __restrict__ rrec,
+                                                                int* __restrict__ masks, unsigned* __restrict__ keys,
+                                                                int* __restrict__ vals) {
+    __shared__ CfgWideShm sh;
+    const int x = threadIdx.x;
+    const long r = (long)blockIdx.x * kRowsPerBlock + x;
+    int mem[KW] = {}, c0 = 0, c1 = 0, k = 0;
+    if (r >= r0 && r < r1) {
+        const int code = cfg_row<KW>(rows + r * ng, ng, C, mem, c0, c1);
+        k = code > 0 ? code : 0;  // failing rows were rejected before this launch
+    }
+    int ps, pr, ts, tr;
+    block_exscan2(k > 0, k, ps, pr, ts, tr);
+    if (ts == 0) return;  // (the whole block: outside the slice, or null rows only)
+    if (x <= KW) sh.hist[x] = 0;
+    int S0 = 0, S1 = 0;
+#pragma unroll
+    for (int j = 0; j < KW; j++)
+        if (j < k) {
+            const unsigned pr_ = P.pres[mem[j]];
+            if (pr_ & 1u) S0 |= 1 << j;
+            if (pr_ & 2u) S1 |= 1 << j;
+        }
+    const bool valid = k > 0 && ((c0 | c1) == (1 << k) - 1) && !(c0 & ~S0) && !(c1 & ~S1);
+
+    // walk -> descriptors (a row that adds nothing: two empty tasks)
+    int tt[2];
+#pragma unroll
+    for (int s = 0; s < 2; s++) {
+        const int cs = valid ? (s ? c1 : c0) : 0;
+        unsigned short* d = sh.idx[2 * x + s];
+        int t = 0;
+#pragma unroll
+        for (int j = 0; j < KW; j++)
+            if ((cs >> j) & 1) d[t++] = (unsigned short)mem[j];
+#pragma unroll
+        for (int j = 0; j < KW; j++)
+            if (j >= t) d[j] = 0;
+        sh.t[2 * x + s] = (unsigned char)t;
+        tt[s] = t;
+    }
+    __syncthreads();
+    // counting sort on t (the order within a bin is free: results return to the task's own slot)
+    const int rk0 = atomicAdd(&sh.hist[tt[0]], 1), rk1 = atomicAdd(&sh.hist[tt[1]], 1);
+    __syncthreads();
+    int b0 = 0, b1 = 0, run = 0;
+#pragma unroll
+    for (int b = 0; b <= KW; b++) {
+        if (b == tt[0]) b0 = run;
+        if (b == tt[1]) b1 = run;
+        run += sh.hist[b];
+    }
+    sh.order[b0 + rk0] = (unsigned short)(2 * x);
+    sh.order[b1 + rk1] = (unsigned short)(2 * x + 1);
+    __syncthreads();
+
+    // factor
+#pragma unroll 1
+    for (int h = 0; h < 2; h++) {
+        const int task = sh.order[h ? kTasks - 1 - x : x];
+        const int s = task & 1, t = sh.t[task];
+        int ix[KW];
+#pragma unroll
+        for (int i = 0; i < KW; i++) ix[i] = sh.idx[task][i];
+        int tmax = t;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) tmax = max(tmax, __shfl_xor(tmax, o));
+        tmax = __builtin_amdgcn_readfirstlane(tmax);
+        double q, Pd, mu;
+        int n;
+        ldlt_wide(s ? P.G[1] : P.G[0], P.ldg, s ? P.Ad[1] : P.Ad[0], s ? P.y[1] : P.y[0], s ? P.dval[1] : P.dval[0],
+                  ix, t, tmax, q, Pd);
+        split_exp(0.5 * q * PSX_LOG2E, 1.0 / sqrt(Pd), n, mu);
+        sh.n[task] = n;
+        sh.mu[task] = mu;
+        sh.f[task] = 0.5 * q - 0.5 * log(Pd);
+    }
+    __syncthreads();
+
+    // combine: k_cfg_eval's outputs at the row's offsets
+    if (k == 0) return;
+    const long si = (long)blk[blockIdx.x] + ps;
+    const long ri = (long)blk[nblk + blockIdx.x] + pr;
+    const CfgPrior& pri = *P.prior;
+    const int Ck = pri.Ck[k];
+    SetRec rr = set_zero();
+    CfgRow row{0.0, 0.0, 0, 0, 0, 0};
+    if (valid) {
+        const int nsh = __popc(c0 & c1);
+        const double pit = pri.pit[k][nsh], pit0 = pri.pit[k][0];
+        const double mup = sh.mu[2 * x] * sh.mu[2 * x + 1];
+        const int np = sh.n[2 * x] + sh.n[2 * x + 1];
+        const int G = np + 2;  // k_eval_sets' "+ 2" headroom, at this assignment's exponent
+        const double wll = ldexp(mup, -2);
+        const double w = wll * pit;
+        rr.m = G + Ck;
+        rr.tot = w;
+        rr.m0 = rr.m1 = np + Ck;
+        rr.nc0 = c0 == 0 ? mup * pit0 : 0.0;
+        rr.nc1 = c1 == 0 ? mup * pit0 : 0.0;
+        rr.score = sh.f[2 * x] + sh.f[2 * x + 1] + pri.prior[k][nsh];
+        rr.npat = 1.0;
+        row = CfgRow{w, wll, G, Ck, 1, 0};
+    }
+    srec[si] = rr;
+    rrec[si] = row;
+    masks[si] = c0 | (c1 << 16);
+#pragma unroll
+    for (int j = 0; j < KW; j++)
+        if (j < k) {
+            keys[ri + j] = (unsigned)mem[j];
+            vals[ri + j] = (int)(si * KW + j);
+        }
+}
+
 // member j of row `set`: the record k_eval_rows writes for it
+template <int KM>
 __device__ __forceinline__ Acc5 cfg_record(const CfgRow* __restrict__ rrec, const int* __restrict__ masks, int q) {
-    const int set = q / PSX_KMAX, j = q - set * PSX_KMAX;
+    const int set = q / KM, j = q - set * KM;
     const CfgRow row = rrec[set];
     Acc5 a = acc_zero();
     if (!row.valid) return a;
     const int m = masks[set];
-    const int x = ((m >> j) & 1) | (((m >> (8 + j)) & 1) << 1);
+    const int x = ((m >> j) & 1) | (((m >> (16 + j)) & 1) << 1);
     a.mP = row.G + row.Ck;
     a.mS = a.mN = row.G;
     a.post0 = (x & 1) ? row.w : 0.0;
@@ -347,6 +565,7 @@ __device__ __forceinline__ Acc5 cfg_record(const CfgRow* __restrict__ rrec, cons
 constexpr int kMergeR = 8;
 constexpr int kSliceRecs = 8192;  // records per level-1 slice (S = ceil(most / kSliceRecs))
 constexpr int kMaxSlices = 256;
+template <int KM>
 __global__ __launch_bounds__(256) void k_cfg_merge(const CfgRow* __restrict__ rrec, const int* __restrict__ masks,
                                                    const int* __restrict__ ptr, const int* __restrict__ idx, int S,
                                                    Acc5* __restrict__ parts) {
@@ -361,7 +580,7 @@ __global__ __launch_bounds__(256) void k_cfg_merge(const CfgRow* __restrict__ rr
         for (int q = 0; q < kMergeR; q++) ix[q] = i0 + 256 * q < e ? idx[i0 + 256 * q] : -1;
         Acc5 v[kMergeR];
 #pragma unroll
-        for (int q = 0; q < kMergeR; q++) v[q] = ix[q] >= 0 ? cfg_record(rrec, masks, ix[q]) : acc_zero();
+        for (int q = 0; q < kMergeR; q++) v[q] = ix[q] >= 0 ? cfg_record<KM>(rrec, masks, ix[q]) : acc_zero();
 #pragma unroll
         for (int q = 0; q < kMergeR; q++) fold_acc(a, v[q]);
     }
@@ -476,8 +695,8 @@ bool grow(T*& p, size_t& cap, size_t n) {
 }  // namespace
 
 int configs_pass(CfgWork& W, const int16_t* rows, int64_t n_rows, int n_groups, int64_t r0, int64_t r1,
-                 const CfgMaps& C, const CfgProb& P, Acc5* acc, SetRec* sacc, hipStream_t st, hipEvent_t k0,
-                 hipEvent_t k1, CfgResult* out, const char** err) {
+                 const CfgMaps& C, const CfgProb& P, const CfgPrior* dprior, Acc5* acc, SetRec* sacc, hipStream_t st,
+                 hipEvent_t k0, hipEvent_t k1, CfgResult* out, const char** err) {
     *out = CfgResult{-1, 0, 0, 0, 0};
     auto bad = [&](const char* m) {
         *err = m;
@@ -494,19 +713,34 @@ int configs_pass(CfgWork& W, const int16_t* rows, int64_t n_rows, int n_groups, 
         return bad("out of device memory");
     if (!W.hstatus && psx::hmalloc(&W.hstatus, 5 * sizeof(unsigned long long)) != hipSuccess)
         return bad("out of pinned host memory");
-    if (upload_rows(W, rows, nel * sizeof(int16_t), W.rows, st) ||
-        hipMemsetAsync(W.status, 0xff, sizeof(unsigned long long), st) != hipSuccess ||
-        hipMemsetAsync(W.status + 1, 0, 4 * sizeof(unsigned long long), st) != hipSuccess ||
-        hipMemsetAsync(W.ptr, 0, ((size_t)C.U + 1) * sizeof(int), st) != hipSuccess)
-        return bad("configs upload");
+    if (upload_rows(W, rows, nel * sizeof(int16_t), W.rows, st)) return bad("configs upload");
     const int lds = C.U <= kLdsHistMax ? 1 : 0;
-    hipLaunchKernelGGL(k_cfg_count, dim3((unsigned)nblk), dim3(kRowsPerBlock), lds ? C.U * sizeof(int) : 0, st,
-                       W.rows, (long)n_rows, n_groups, C, (long)r0, (long)r1, W.status, W.blk, (int)nblk, W.ptr, lds);
-    hipLaunchKernelGGL(k_cfg_scan, dim3(1), dim3(1024), 0, st, W.blk, (int)nblk, W.ptr, C.U, W.status);
-    if (hipGetLastError() != hipSuccess) return bad("configs count launch");
-    if (hipMemcpyAsync(W.hstatus, W.status, 5 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess)
-        return bad("configs status");
+    // the count of all rows under the rules of `wide`, its scans, the status read
+    auto count = [&](bool wide) -> const char* {
+        if (hipMemsetAsync(W.status, 0xff, sizeof(unsigned long long), st) != hipSuccess ||
+            hipMemsetAsync(W.status + 1, 0, 4 * sizeof(unsigned long long), st) != hipSuccess ||
+            hipMemsetAsync(W.ptr, 0, ((size_t)C.U + 1) * sizeof(int), st) != hipSuccess)
+            return "configs upload";
+        hipLaunchKernelGGL(wide ? k_cfg_count<KW> : k_cfg_count<PSX_KMAX>, dim3((unsigned)nblk), dim3(kRowsPerBlock),
+                           lds ? C.U * sizeof(int) : 0, st, W.rows, (long)n_rows, n_groups, C, (long)r0, (long)r1,
+                           W.status, W.blk, (int)nblk, W.ptr, lds);
+        hipLaunchKernelGGL(k_cfg_scan, dim3(1), dim3(1024), 0, st, W.blk, (int)nblk, W.ptr, C.U, W.status);
+        if (hipGetLastError() != hipSuccess) return "configs count launch";
+        if (hipMemcpyAsync(W.hstatus, W.status, 5 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) !=
+                hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess)
+            return "configs status";
+        return nullptr;
+    };
+    if (const char* m = count(false)) return bad(m);
+    // a row of more than PSX_KMAX union SNPs comes first among the failing rows:
+    // the whole file again under the wide rules (a failing row before it under the
+    // narrow rules fails there too: the codes 1 and 3 do not depend on KM)
+    const bool wide = W.hstatus[0] != ~0ull && (W.hstatus[0] & 7) == 2;
+    if (wide) {
+        if ((r1 - r0) * KW >= (int64_t)INT32_MAX) return bad("configs file too large");
+        if (const char* m = count(true)) return bad(m);
+    }
     const unsigned long long f = W.hstatus[0];
     if (f != ~0ull) {  // the first failing row in row order (postcal.cpp:432-590 exits there)
         out->fail_row = (int64_t)(f >> 3);
@@ -573,16 +807,31 @@ int configs_pass(CfgWork& W, const int16_t* rows, int64_t n_rows, int n_groups, 
         W.cap_sort = tmp;
     }
     if (k0 && hipEventRecord(k0, st) != hipSuccess) return bad("event");
-    hipLaunchKernelGGL(k_cfg_eval, dim3((unsigned)nblk), dim3(kRowsPerBlock), 0, st, W.rows, n_groups, C, (long)r0,
-                       (long)r1, P, W.blk, (int)nblk, W.srec, (CfgRow*)W.rrec, W.masks, W.keys, W.vals);
+    if (wide) {
+        CfgProbWide PW;
+        for (int s = 0; s < 2; s++) {
+            PW.G[s] = P.G[s];
+            PW.Ad[s] = P.Ad[s];
+            PW.y[s] = P.y[s];
+            PW.dval[s] = P.dval[s];
+        }
+        PW.pres = P.pres;
+        PW.prior = dprior;
+        PW.ldg = P.ldg;
+        hipLaunchKernelGGL(k_cfg_eval_wide, dim3((unsigned)nblk), dim3(kRowsPerBlock), 0, st, W.rows, n_groups, C,
+                           (long)r0, (long)r1, PW, W.blk, (int)nblk, W.srec, (CfgRow*)W.rrec, W.masks, W.keys, W.vals);
+    } else {
+        hipLaunchKernelGGL(k_cfg_eval, dim3((unsigned)nblk), dim3(kRowsPerBlock), 0, st, W.rows, n_groups, C, (long)r0,
+                           (long)r1, P, W.blk, (int)nblk, W.srec, (CfgRow*)W.rrec, W.masks, W.keys, W.vals);
+    }
     if (k1 && hipEventRecord(k1, st) != hipSuccess) return bad("event");
     if (hipGetLastError() != hipSuccess) return bad("configs eval launch");
     size_t tmp2 = W.cap_sort;
     if (hipcub::DeviceRadixSort::SortPairs(W.sort_tmp, tmp2, W.keys, keys_out, W.vals, vals_out, (int)nr, 0, end_bit,
                                            st) != hipSuccess)
         return bad("configs sort");
-    hipLaunchKernelGGL(k_cfg_merge, dim3((unsigned)C.U, (unsigned)S), dim3(256), 0, st, (const CfgRow*)W.rrec,
-                       W.masks, W.ptr, vals_out, S, (Acc5*)W.parts);
+    hipLaunchKernelGGL(wide ? k_cfg_merge<KW> : k_cfg_merge<PSX_KMAX>, dim3((unsigned)C.U, (unsigned)S), dim3(256), 0,
+                       st, (const CfgRow*)W.rrec, W.masks, W.ptr, vals_out, S, (Acc5*)W.parts);
     hipLaunchKernelGGL(k_cfg_merge2, dim3((unsigned)((C.U + 63) / 64)), dim3(64), 0, st, (const Acc5*)W.parts, S, C.U,
                        acc);
     if (hipGetLastError() != hipSuccess) return bad("configs merge launch");

@@ -1046,6 +1046,8 @@ struct psx_engine {
     double a_kms = 0;
     // configs-file enumerator (psx_configs.hip): index maps on the device, workspace
     int* d_cfg_maps = nullptr;  // l2u[N] | u2l[2 * U]
+    psx::CfgPrior cfg_prior;    // the prior tables for rows of k <= PSX_KWIDE union SNPs (dp's, continued)
+    psx::CfgPrior* d_cfg_prior = nullptr;
     psx::CfgWork cfg;
     // SSS walk workspace: the set map, per-item rows / marks and the pinned
     // host buffers, grown on demand and reused by the next walk
@@ -1077,6 +1079,7 @@ psx_engine::~psx_engine() {
     psx::sweep_free(plans);
     psx::configs_free(cfg);
     psx::dfree(d_cfg_maps);
+    psx::dfree(d_cfg_prior);
     sss_release(sss);
     for (auto& kv : glevels) {
         GenLevel& g = kv.second;
@@ -1944,17 +1947,27 @@ int create_impl(const psx_problem* p, const psx_ld_problem* ld, int device, psx_
     dp.ldg = e->ldg;
     dp.dval[0] = e->dval[0];
     dp.dval[1] = e->dval[1];
-    for (int k = 0; k <= PSX_KMAX; k++) {
+    // (to PSX_KWIDE for the configs file's wide rows; dp keeps k <= PSX_KMAX)
+    psx::CfgPrior& cp = e->cfg_prior;
+    std::memset(&cp, 0, sizeof(cp));
+    for (int k = 0; k <= PSX_KWIDE; k++) {
         double mx = -INFINITY;
         for (int n = 0; n <= k; n++) {
             double pr = prior_nats(p, e->U, k, n);
-            dp.prior[k][n] = pr;
+            cp.prior[k][n] = pr;
             if (std::isfinite(pr)) mx = std::max(mx, pr * PSX_LOG2E);
         }
-        dp.Ck[k] = std::isfinite(mx) ? (int)std::ceil(mx) : 0;
+        cp.Ck[k] = std::isfinite(mx) ? (int)std::ceil(mx) : 0;
         for (int n = 0; n <= k; n++) {
-            double v = dp.prior[k][n] * PSX_LOG2E - dp.Ck[k];
-            dp.pit[k][n] = std::isfinite(v) ? std::exp2(v) : 0.0;
+            double v = cp.prior[k][n] * PSX_LOG2E - cp.Ck[k];
+            cp.pit[k][n] = std::isfinite(v) ? std::exp2(v) : 0.0;
+        }
+    }
+    for (int k = 0; k <= PSX_KMAX; k++) {
+        dp.Ck[k] = cp.Ck[k];
+        for (int n = 0; n <= k; n++) {
+            dp.prior[k][n] = cp.prior[k][n];
+            dp.pit[k][n] = cp.pit[k][n];
         }
     }
 
@@ -2567,6 +2580,10 @@ int psx_run_configs(psx_engine* e, const int16_t* rows, int64_t n_rows, int32_t 
         HIPCHK(psx::dmalloc(&e->d_cfg_maps, maps.size() * sizeof(int)));
         HIPCHK(hipMemcpy(e->d_cfg_maps, maps.data(), maps.size() * sizeof(int), hipMemcpyHostToDevice));
     }
+    if (!e->d_cfg_prior) {
+        HIPCHK(psx::dmalloc(&e->d_cfg_prior, sizeof(psx::CfgPrior)));
+        HIPCHK(hipMemcpy(e->d_cfg_prior, &e->cfg_prior, sizeof(psx::CfgPrior), hipMemcpyHostToDevice));
+    }
     psx::CfgMaps C{e->d_cfg_maps, e->d_cfg_maps + e->N, e->U, e->N, e->m[0], e->m[1]};
     psx::CfgProb P;
     for (int s = 0; s < 2; s++) {
@@ -2586,13 +2603,13 @@ int psx_run_configs(psx_engine* e, const int16_t* rows, int64_t n_rows, int32_t 
     HIPCHK(hipEventRecord(e->ev[0], e->stream));
     psx::CfgResult res;
     const char* err = nullptr;
-    if (psx::configs_pass(e->cfg, rows, n_rows, n_groups, r0, r1, C, P, e->dacc, e->dsacc, e->stream, e->ev[2],
-                          e->ev[3], &res, &err))
+    if (psx::configs_pass(e->cfg, rows, n_rows, n_groups, r0, r1, C, P, e->d_cfg_prior, e->dacc, e->dsacc, e->stream,
+                          e->ev[2], e->ev[3], &res, &err))
         return fail(PSX_EHIP, std::string("configs file: ") + err);
     if (res.fail_row >= 0) {  // the first failing row in row order
         reset_acc(e);
         if (res.fail_code == 1) return fail(PSX_EINVAL, "configs row index outside the SNP range");
-        if (res.fail_code == 2) return fail(PSX_ERANGE, "configs row has more than 6 union SNPs");
+        if (res.fail_code == 2) return fail(PSX_ERANGE, "configs row has more than 10 union SNPs");
         return fail(PSX_EORDER, "This did not work as expected (postcal.cpp:587-590)");
     }
     if ((rc = fold_null(e, (double)res.nulls))) return rc;
