@@ -20,6 +20,10 @@
 //    unit and read with immediate offsets;
 //  * y is pre-scaled by sqrt(log2(e)/2), so every quadratic form is directly
 //    the base-2 exponent h_T of the subset weight;
+//  * the fast walk takes the {a, b, c} weight as the slot's {a, b} weight (staged
+//    per a) times c's extension factor 2^(t3^2) r3 rsd / 2, so a step reads
+//    neither the {a, b} quadratic form nor its pivot factor from LDS (the LDS
+//    pipe is as busy as the VALU here: one pipe per CU, eight waves on it);
 //  * 1/sqrt(pivot) is v_rsq_f64 (5e-8 relative on gfx950, tools/rsq_acc.hip)
 //    plus ONE Newton step (4e-15), kept scaled by 2 so it costs three ops;
 //  * 2^h is split as 2^n * mu by a round-to-nearest magic add, a 256-entry
@@ -37,6 +41,10 @@
 // zeroes every subset weight containing them (checkOR of postcal.cpp:907-955).
 // notSharedLL groups more than ~900 bits below a set's scale raise *flag; the
 // host then reruns the level with k_sweep<3, true> (exact group scaling).
+//
+// -DPSX_K3_ABLATE_LDS (through K3FLAGS; off by default, results knowingly wrong)
+// is a timing ablation: the walk takes a constant for its two exp2 table reads
+// (EXPERIMENTS.md section E).
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -157,19 +165,18 @@ __device__ __forceinline__ void split3a(double h, double rP, int& N, double& q) 
     q = p * rP;
 }
 
-// split3a with the rounding offset by an integer R (cmag = kMagic - 256 R):
-// N = round(256 (h - R)), so the caller's exponent is N >> 8 = n - R directly;
-// the fraction's exponential by the walk's cubic (kC*).  k256 = 256 and kc3 = kC3
-// in SGPRs, kc2 = kC2 in a VGPR: opaque values the caller holds for the walk, so
-// the compiler emits one VOP3 v_fma_f64 instead of copying the addend (a
+// split3a of h = (t16 / 16)^2 from t16 itself: N = round(t16^2) = round(256 h),
+// f = t16^2 - N by one FMA (the product is never rounded); the fraction's
+// exponential by the walk's cubic (kC*).  kmag = kMagic and kc3 = kC3 in SGPRs,
+// kc2 = kC2 in a VGPR: opaque values the caller holds for the walk, so the
+// compiler emits one VOP3 v_fma_f64 instead of copying the addend (a
 // loop-carried VGPR, or a constant it cannot put on the constant bus beside
 // another) for the two-address v_fmac_f64 with a literal: a v_mov_b64 per use
-__device__ __forceinline__ void split3r(double h, double rP, double cmag, double k256, double kc3, double kc2,
-                                        int& N, double& q) {
-    const double xr = fma(h, k256, cmag);
+__device__ __forceinline__ void split3w(double t16, double rP, double kmag, double kc3, double kc2, int& N, double& q) {
+    const double xr = fma(t16, t16, kmag);
     N = __double2loint(xr);
-    const double kf = xr - cmag;
-    const double f = fma(h, k256, -kf);
+    const double kf = xr - kmag;
+    const double f = fma(t16, t16, -kf);
     double p = fma(f, kc3, kc2);
     p = fma(p, f, kC1);
     p = fma(p, f, kC0);
@@ -333,8 +340,14 @@ struct Sweep3FastSmem {
     double2 aAd[kMaxChunkA3], aY[kMaxChunkA3];  // the unit's a: A_aa, y_a (both studies), presence
     unsigned aP[kMaxChunkA3];
     int aPos[kMaxChunkA3];  // a record positions
-    double2 abG[64], abI[64], abIW[64], abH[64], abR[64];
-    double2 abMu[64], abMuB[64];  // the slot's {a, b} / {b} weights relative to 2^Ru_s (wave reference)
+    // the slot's (a, b) terms of the c step, pre-scaled (see the a prologue) so that the
+    // step's 2 / sqrt(pivot) comes out times rsd / 2 and its t times 16
+    double2 abG[64], abI[64], abIW[64];
+    // the slot's {a, b} / {b} weights relative to 2^Ru_s (wave reference).  The
+    // {a, b, c} weight is the {a, b} weight times c's extension factor, so the
+    // step needs neither the {a, b} quadratic form nor its pivot factor
+    double2 abMu[64], abMuB[64];
+    int abE[64];  // the slot's {a, b} exponents under the reference, both studies summed (redo test)
     float bW[64];  // membership weight of the slot's b (0, 1 or 3)
     double sW0[64], sW1[64], sW2[64], sSl[64], sNs[64];
     double sW2w[64], sSlw[64];  // the current a's walk part of sW2 / sSl, at 2^(Ru_0 + Ru_1)
@@ -358,6 +371,7 @@ struct Sweep3FastSmem {
     };
     double pbS[2];              // sum of the block's {b} weights, both studies: 2^pbM * pbS
     double kc2;                 // the walk's kC2 (non-SEP units read it per a)
+    double2 scD, scW;           // the walk's pre-scales, both studies: (2 / rsd)^2 and 16 (2 / rsd)
     int pbM[2];
 };
 union SweepSmem {  // a block runs either a k = 3 unit or a level-2 unit
@@ -758,7 +772,16 @@ __device__ __forceinline__ void sweep3_unit_fast(const Sweep3Args& A, int unit, 
     // ---- unit prologue: the unit's constants are loaded once, into LDS where other
     // lanes read them and into registers where a lane reads only its own ---------------
     for (int i = t; i < 256; i += 64) tab[i] = A.tab[i];
-    if (t == 0) F.kc2 = kC2;
+    if (t == 0) {
+        // The c step's pivot factor r3 rsd / 2 (r3 = 2 / sqrt(D3)) costs no multiply:
+        // D1 and the slots' I_ab are staged times (2 / rsd)^2, so rsq2x returns it
+        // directly; w1 / 2 and I_ab w_ab / 2 are staged times 16 (2 / rsd), so
+        // w3 r3 = 16 t3 and the split squares it in its FMAs (split3w)
+        const double i0 = 2.0 / A.rsd[0], i1 = 2.0 / A.rsd[1];
+        F.kc2 = kC2;
+        F.scD = make_double2(i0 * i0, i1 * i1);
+        F.scW = make_double2(16.0 * i0, 16.0 * i1);
+    }
     const int vbl = 64 * K + t, ubl = vbl - pad;
     const bool okb = vbl >= pad;
     const int ib = okb ? ubl : 0;  // clamped index: the loads are unconditional
@@ -800,7 +823,9 @@ __device__ __forceinline__ void sweep3_unit_fast(const Sweep3Args& A, int unit, 
 
     // c accumulator (shift mC), noCausal (shifts m0, m1), redo gap
     int mC = EMPTY, m0 = EMPTY, m1 = EMPTY, dmax = 0;
-    bool wide = false;  // some a's lanes spread more than kMaxSpread below the wave: redo
+    // the wave's reference does not fit some a: lanes spread more than kMaxSpread
+    // below it, or a slot's {a, b} weight more than kMaxRefGap bits under it: redo
+    bool wide = false;
     double cW0 = 0.0, cW1 = 0.0, cW2 = 0.0, cSl = 0.0, cNs = 0.0;
     double nc0 = 0.0, nc1 = 0.0, npat = 0.0;
     const double2* g01 = A.g01 + (size_t)tile * 4096 + t;
@@ -941,7 +966,9 @@ __device__ __forceinline__ void sweep3_unit_fast(const Sweep3Args& A, int unit, 
         }
         const unsigned pa = F.aP[ai];
         const double2 aAd = F.aAd[ai], aY = F.aY[ai];
-        double pG[2], pI[2], pIW[2], pH[2], pR[2], pMu[2], pMuB[2];
+        const double2 vD = F.scD, vW = F.scW;  // (re-read per a: not live across the walk)
+        const double scD[2] = {vD.x, vD.y}, scW[2] = {vW.x, vW.y};
+        double pG[2], pI[2], pIW[2], pMu[2], pMuB[2];
         int pN[2];
 #pragma unroll
         for (int s = 0; s < 2; s++) {
@@ -969,10 +996,8 @@ __device__ __forceinline__ void sweep3_unit_fast(const Sweep3Args& A, int unit, 
                 const int nB = uNB[s];
                 const double muB = uB[s];
                 pG[s] = Gab;
-                pI[s] = rab * rab;
-                pIW[s] = rab * rab * (0.5 * wab);  // I_ab w_ab / 2 (the pivot itself is not needed)
-                pH[s] = hab;
-                pR[s] = rPab * (0.5 * A.rsd[s]);
+                pI[s] = rab * rab * scD[s];
+                pIW[s] = rab * rab * (0.5 * scW[s] * wab);  // I_ab w_ab / 2 (the pivot itself is not needed)
                 pMu[s] = muAB;
                 pMuB[s] = ldexp(muB, nB - nAB);
                 pN[s] = nAB;
@@ -981,8 +1006,9 @@ __device__ __forceinline__ void sweep3_unit_fast(const Sweep3Args& A, int unit, 
             l1[s] = Gac * iAaa;
             D1[s] = fma(-l1[s], Gac, vAcc[s]);
             const double w1 = fma(-l1[s], ya, vyc[s]);
-            w1h[s] = 0.5 * w1;
+            w1h[s] = 0.5 * scW[s] * w1;
             const double r1 = rsqrt_nr(D1[s]);
+            D1[s] *= scD[s];  // (the walk's pivot, scaled as the slots' I_ab)
             const double h1 = fma(w1 * w1, r1 * r1, ha);
             const double chic = (okc && (ALLPRES || ((pcm >> s) & 1u))) ? 1.0 : 0.0;
             const double rP1 = rPa * r1 * A.rsd[s] * chic;
@@ -998,8 +1024,6 @@ __device__ __forceinline__ void sweep3_unit_fast(const Sweep3Args& A, int unit, 
         F.abG[t] = make_double2(pG[0], pG[1]);
         F.abI[t] = make_double2(pI[0], pI[1]);
         F.abIW[t] = make_double2(pIW[0], pIW[1]);
-        F.abH[t] = make_double2(pH[0], pH[1]);
-        F.abR[t] = make_double2(pR[0], pR[1]);
         const double wac = wc * memb_weight(pa);
         if (A.trace && ai == 0) t_fn[1] = wall_clock64();
         // this a's reference G: the a accumulator sits at it; c / noCausal / the b
@@ -1046,10 +1070,10 @@ __device__ __forceinline__ void sweep3_unit_fast(const Sweep3Args& A, int unit, 
             m0 = M0;
             m1 = M1;
         }
-        // the walk's split constants as opaque registers (split3r)
-        double k256 = 256.0, kc3 = kC3, kc2 = kC2;
+        // the walk's split constants as opaque registers (split3w)
+        double kmag = kMagic, kc3 = kC3, kc2 = kC2;
         if (!SEP) kc2 = F.kc2;  // (re-read per a: not live across the walk)
-        asm volatile("" : "+s"(k256), "+s"(kc3), "+v"(kc2));
+        asm volatile("" : "+s"(kmag), "+s"(kc3), "+v"(kc2));
         // this a's wave maxima in one batch: G (the slot shift) and, for the closed
         // forms of off-diagonal units, R_s and the slots' {a, b} exponents
         // (and the previous a's record shift)
@@ -1075,8 +1099,15 @@ __device__ __forceinline__ void sweep3_unit_fast(const Sweep3Args& A, int unit, 
         const double lam0 = ldexp(1.0, min(sp0, kMaxSpread)), lam1 = ldexp(1.0, min(sp1, kMaxSpread));
         F.abMuB[t] = make_double2(ldexp(pMuB[0], pN[0] - Ru[0]), ldexp(pMuB[1], pN[1] - Ru[1]));
         F.abMu[t] = make_double2(ldexp(pMu[0], pN[0] - Ru[0]), ldexp(pMu[1], pN[1] - Ru[1]));
-        // round-to-nearest magic offset by Ru: N = round(256 (h3 - Ru)), so n3 - Ru = N >> 8
-        const double cmag[2] = {kMagic - 256.0 * Ru[0], kMagic - 256.0 * Ru[1]};
+        // The step takes the {a, b, c} weight as this {a, b} weight times c's
+        // extension factor 2^(t3^2) r3 rsd / 2, whose exponent alone the split
+        // yields; n_abc - Ru of the redo test is that plus the slot's n_ab - Ru
+        // (as integers: no product is read that may have overflowed)
+        F.abE[t] = (pN[0] - Ru[0]) + (pN[1] - Ru[1]);
+        // a slot whose {a, b} weight falls out of the normal range under the
+        // reference could not carry a large extension: redone (robust)
+        wide |= __builtin_amdgcn_ballot_w64((pMu[0] != 0.0 && pN[0] - Ru[0] < -kMaxRefGap) ||
+                                            (pMu[1] != 0.0 && pN[1] - Ru[1] < -kMaxRefGap)) != 0;
         // the previous a's record: its sums at the wave's largest shift
         const int rGw = mx[1], rdg = rG != EMPTY ? rG - rGw : -2000;
         double abS[2] = {0.0, 0.0};  // sum over the slots of the {a, b} weights, at 2^abM
@@ -1209,22 +1240,21 @@ __device__ __forceinline__ void sweep3_unit_fast(const Sweep3Args& A, int unit, 
                 reinterpret_cast<const char*>(arr) + off);
         };
         auto chain = [&](unsigned o16, double2 g, int (&N)[2], double (&q)[2]) {
-            const double2 aG = slot(F.abG, o16), aI = slot(F.abI, o16), aIW = slot(F.abIW, o16),
-                          aH = slot(F.abH, o16), aR = slot(F.abR, o16);
+            const double2 aG = slot(F.abG, o16), aI = slot(F.abI, o16), aIW = slot(F.abIW, o16);
 #pragma unroll
             for (int s = 0; s < 2; s++) {
                 // x = the unnormalised L entry of c against b; D_ab I_ab = 1 folds the pivot away
+                // (D1, I_ab, w1h, I_ab w_ab pre-scaled: r3 = rsd / sqrt(D3), t16 = 16 t3)
                 const double Gbc = s ? g.y : g.x;
                 const double x = fma(-l1[s], s ? aG.y : aG.x, Gbc);
                 const double lcb = x * (s ? aI.y : aI.x);
                 const double D3 = fma(-x, lcb, D1[s]);
                 const double w3 = fma(-x, s ? aIW.y : aIW.x, w1h[s]);
-                const double r3 = rsq2x(D3);
-                const double t3 = w3 * r3;
-                const double h3 = fma(t3, t3, s ? aH.y : aH.x);
-                double rP3 = (s ? aR.y : aR.x) * r3;
-                if (!ALLPRES && !((pcm >> s) & 1u)) rP3 = 0.0;  // c absent from study s
-                split3r(h3, rP3, cmag[s], k256, kc3, kc2, N[s], q[s]);
+                double r3 = rsq2x(D3);
+                const double t16 = w3 * r3;
+                if (!ALLPRES && !((pcm >> s) & 1u)) r3 = 0.0;  // c absent from study s
+                // c's extension of the slot's {a, b} weight: 2^(t3^2) r3 = 2^(N >> 8) tab[N & 255] q
+                split3w(t16, r3, kmag, kc3, kc2, N[s], q[s]);
             }
         };
         // SEP (off-diagonal units): the {} / {a} parts of the prior-weighted one-study
@@ -1238,9 +1268,16 @@ __device__ __forceinline__ void sweep3_unit_fast(const Sweep3Args& A, int unit, 
         struct FTt {
             double2 muB, mu;  // the slot's {b} / {a, b} weights relative to 2^Ru_s
             double tb0, tb1;
+            int e;  // the slot's n_ab - Ru, both studies summed
         };
         auto ld_ft = [&](unsigned o16, const int (&N)[2]) {
-            return FTt{slot(F.abMuB, o16), slot(F.abMu, o16), tab[N[0] & 255], tab[N[1] & 255]};
+#ifdef PSX_K3_ABLATE_LDS
+            // timing ablation (results knowingly wrong): no exp2 table reads, the bound
+            // on what a conflict-free table could win (EXPERIMENTS.md)
+            return FTt{slot(F.abMuB, o16), slot(F.abMu, o16), 1.0, 1.0, slot(F.abE, o16 >> 2)};
+#else
+            return FTt{slot(F.abMuB, o16), slot(F.abMu, o16), tab[N[0] & 255], tab[N[1] & 255], slot(F.abE, o16 >> 2)};
+#endif
         };
         auto finish_ft = [&](unsigned o8, const FTt& ft, const int (&N)[2], const double (&q)[2], double2 mcur,
                              int2 ncur) {
@@ -1249,11 +1286,11 @@ __device__ __forceinline__ void sweep3_unit_fast(const Sweep3Args& A, int unit, 
             const double2 aMuB = ft.muB, aMu = ft.mu;
             // v[s][A] = E_s[A + b] relative to 2^{Ru_s}: {b}, {a, b}, {b, c}, {a, b, c}
             double v[2][4];
-            int d3s = 0;
+            int d3s = ft.e;
 #pragma unroll
             for (int s = 0; s < 2; s++) {
-                const int d3 = N[s] >> 8;  // n3 - Ru (N is Ru-relative)
-                const double mu3 = (s ? ft.tb1 : ft.tb0) * q[s];
+                const int d3 = N[s] >> 8;  // c's extension exponent: n3 - n_ab (within one bit)
+                const double mu3 = (s ? ft.tb1 : ft.tb0) * q[s] * (s ? aMu.y : aMu.x);
                 const int n2 = s ? ncur.y : ncur.x;
                 const double mu2 = s ? mcur.y : mcur.x;
                 d3s += d3;
@@ -1418,7 +1455,9 @@ __device__ __forceinline__ void sweep3_unit_fast(const Sweep3Args& A, int unit, 
             int ru0 = Ru[0], ru1 = Ru[1];
             asm volatile("" : "+s"(ru0), "+s"(ru1));
             const int q0 = ru0 - R[0], q1 = ru1 - R[1];
-            dmax = max(dmax, dA + q0 + q1);
+            // (dA sums two split exponents per study, n_ab - Ru and c's extension: at
+            // most one bit per study under the split of their sum, n_abc - Ru)
+            dmax = max(dmax, dA + 2 + q0 + q1);
             const double m0f = ldexp(1.0, min(q0, kMaxSpread)), m1f = ldexp(1.0, min(q1, kMaxSpread));
 #pragma unroll
             for (int i = sep ? 3 : 0; i < 4; i++) {
