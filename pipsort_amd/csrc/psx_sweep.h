@@ -99,6 +99,9 @@ struct Sweep3Args {
     const double2* g01;        // skewT of both studies interleaved (one 16-byte load per step)
     const double2* mu01;       // {b, c} subset weights mu per [tile][step][lane], both studies (a-independent)
     const int2* bcn;           // their base-2 exponents, both studies
+    const double2* bcr;        // the same weights ready for the fast walk: mu01 * 2^(bcn - bcrn), laid out as mu01
+    const int2* bcrn;          // per [tile][lane]: the lane's reference exponent of bcr, both studies
+    const int* bcwide;         // per tile: non-zero where a lane's weights span too far for bcr (robust units)
     const double2* bcsm;       // per [tile][lane]: sum over the tile's 64 b of the {b, c} weights, both
     const int2* bcsn;          //   studies, as 2^bcsn * bcsm (the off-diagonal walk's closed-form sums)
     const double2* bccm;       // per [tile][b slot]: sum over the tile's 64 c of the {b, c} weights
@@ -129,6 +132,10 @@ int launch_build_skewT(const double* G, int ldg, int pad, double* skew, hipStrea
 // step), computed once per locus with the sweep kernel's own arithmetic
 constexpr int kTileRowPad = 4;  // zero rows after the last tile of mu01 / bcn / g01
 int launch_build_bc3(const Sweep3Args& A, int ntile, double2* mu01, int2* n, hipStream_t st);
+// the fast walk's ready-scaled copy of the {b, c} weights, its per-lane reference
+// exponents and the per-tile flag of a span too wide for it
+int launch_bc3_ready(int ntile, const double2* mu01, const int2* n, double2* bcr, int2* bcrn, int* bcwide,
+                     hipStream_t st);
 // per tile and lane c: the sum over the tile's 64 b of the {b, c} weights
 int launch_bc3_rowsum(int ntile, const double2* mu01, const int2* n, double2* sm, int2* sn, hipStream_t st);
 // per tile and b slot: the sum over the tile's 64 c of the {b, c} weights
@@ -185,6 +192,9 @@ struct SweepPlanCache {
     double2* d_g01 = nullptr;                // skewT of both studies interleaved (k = 3 fast kernel)
     double2* d_mu01 = nullptr;               // {b, c} weights per skewT entry, both studies
     int2* d_bcn = nullptr;
+    double2* d_bcr = nullptr;                // the weights ready-scaled for the fast walk, their per-lane
+    int2* d_bcrn = nullptr;                  //   reference exponents and the per-tile wide flags
+    int* d_bcwide = nullptr;
     double2* d_bcsm = nullptr;               // row sums of the {b, c} weights per tile and lane
     int2* d_bcsn = nullptr;
     double2* d_bccm = nullptr;               // column sums of the {b, c} weights per tile and b slot

@@ -751,6 +751,9 @@ static Sweep3Args sweep3_args(const SweepPlanCache& C, const SweepArgs& a, int U
         S3.muS[s] = A.muS[s]; S3.nS[s] = A.nS[s]; S3.rsd[s] = A.rsd[s];
     }
     S3.bcn = C.d_bcn;
+    S3.bcr = C.d_bcr;
+    S3.bcrn = C.d_bcrn;
+    S3.bcwide = C.d_bcwide;
     S3.bcsm = C.d_bcsm;
     S3.bcsn = C.d_bcsn;
     S3.bccm = C.d_bccm;
@@ -773,6 +776,9 @@ static void free_k3(SweepPlanCache& C) {
         psx::dfree(C.d_ys[s]); C.d_ys[s] = nullptr;
     }
     psx::dfree(C.d_bcn); C.d_bcn = nullptr;
+    psx::dfree(C.d_bcr); C.d_bcr = nullptr;
+    psx::dfree(C.d_bcrn); C.d_bcrn = nullptr;
+    psx::dfree(C.d_bcwide); C.d_bcwide = nullptr;
     psx::dfree(C.d_bcsm); C.d_bcsm = nullptr;
     psx::dfree(C.d_bcsn); C.d_bcsn = nullptr;
     psx::dfree(C.d_bccm); C.d_bccm = nullptr;
@@ -868,6 +874,12 @@ static int ensure_k3_build(SweepPlanCache& C, const SweepArgs& a, int ldg, int U
         SWCHK(hipMemsetAsync(C.d_bcn + nrow, 0, sizeof(int2) * npad, st));
         SWCHK(hipMemsetAsync(C.d_g01 + nrow, 0, sizeof(double2) * npad, st));
         if (launch_build_bc3(S3, ntile, C.d_mu01, C.d_bcn, st)) SWCHK(hipGetLastError());
+        // the fast walk's copy, scaled to a per-lane reference (padded like mu01)
+        SWCHK(psx::dmalloc(&C.d_bcr, sizeof(double2) * (nrow + npad)));
+        SWCHK(psx::dmalloc(&C.d_bcrn, sizeof(int2) * (size_t)ntile * 64));
+        SWCHK(psx::dmalloc(&C.d_bcwide, sizeof(int) * (size_t)ntile));
+        SWCHK(hipMemsetAsync(C.d_bcr + nrow, 0, sizeof(double2) * npad, st));
+        if (launch_bc3_ready(ntile, C.d_mu01, C.d_bcn, C.d_bcr, C.d_bcrn, C.d_bcwide, st)) SWCHK(hipGetLastError());
         SWCHK(psx::dmalloc(&C.d_bcsm, sizeof(double2) * (size_t)ntile * 64));
         SWCHK(psx::dmalloc(&C.d_bcsn, sizeof(int2) * (size_t)ntile * 64));
         if (launch_bc3_rowsum(ntile, C.d_mu01, C.d_bcn, C.d_bcsm, C.d_bcsn, st)) SWCHK(hipGetLastError());

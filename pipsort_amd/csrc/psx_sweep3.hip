@@ -14,7 +14,9 @@
 //
 //  * per step only the {a, b, c} extension is computed: the a-independent
 //    {b, c} weights come precomputed (k_build_bc3, once per locus) and are
-//    streamed with the tile row of Sigma~, both one step ahead of use;
+//    streamed with the tile row of Sigma~, both one step ahead of use; the fast
+//    walk reads them ready-scaled to a per-lane reference (k_bc3_ready), so a
+//    step neither loads their exponents nor rescales them;
 //  * the (a, c) terms (lane-owned) and (a, b) terms (lane-parallel, into LDS)
 //    are hoisted per a; everything else indexed by b is staged in LDS once per
 //    unit and read with immediate offsets;
@@ -828,8 +830,12 @@ __device__ __forceinline__ void sweep3_unit_fast(const Sweep3Args& A, int unit, 
     bool wide = false;
     double cW0 = 0.0, cW1 = 0.0, cW2 = 0.0, cSl = 0.0, cNs = 0.0;
     double nc0 = 0.0, nc1 = 0.0, npat = 0.0;
+    // the tile row: Sigma~ entries and the {b, c} weights.  SEP units read the ready
+    // weights (k_bc3_ready: relative to 2^ref_s, this lane's reference exponent; two
+    // 16-byte loads per step).  The other (diagonal) units walk, per a, only the
+    // pairs above a, which no per-lane reference fits: they keep (mantissa, exponent)
     const double2* g01 = A.g01 + (size_t)tile * 4096 + t;
-    const double2* m01 = A.mu01 + (size_t)tile * 4096 + t;
+    const double2* m01 = (SEP ? A.bcr : A.mu01) + (size_t)tile * 4096 + t;
     const int2* bnn = A.bcn + (size_t)tile * 4096 + t;
     // record positions (CSR map) of this unit's c / b-slot records; this a's
     // Sigma~ row entries (g1ab: this lane's b slot, g1ac: its c)
@@ -916,12 +922,11 @@ __device__ __forceinline__ void sweep3_unit_fast(const Sweep3Args& A, int unit, 
     // (their wait at the loop entry was ~1 us of the first a's prologue, r04p;
     // the other units' registers would spill)
     double2 gnx = make_double2(0.0, 0.0), mnx = make_double2(0.0, 0.0);
-    int2 nnx = make_int2(0, 0);
+    int2 nnx = make_int2(0, 0);  // (SEP: unused)
     double nGab[2] = {0.0, 0.0}, nGac[2] = {0.0, 0.0};
     if (SEP) {
         gnx = g01[j0 * 64];
         mnx = m01[j0 * 64];
-        nnx = bnn[j0 * 64];
 #pragma unroll
         for (int s = 0; s < 2; s++) {
             const double* row = A.G[s] + (size_t)(a1 - a0 > 1 ? a0 + 1 - pad : a0 - pad) * ldg;
@@ -938,7 +943,7 @@ __device__ __forceinline__ void sweep3_unit_fast(const Sweep3Args& A, int unit, 
         if (!SEP || ai > 0) {
             gnx = g01[j0 * 64];
             mnx = m01[j0 * 64];
-            nnx = bnn[j0 * 64];
+            if (!SEP) nnx = bnn[j0 * 64];
 #pragma unroll
             for (int s = 0; s < 2; s++) {
                 const double* row = A.G[s] + (size_t)(nxt ? ua + 1 : ua) * ldg;
@@ -946,6 +951,10 @@ __device__ __forceinline__ void sweep3_unit_fast(const Sweep3Args& A, int unit, 
                 nGac[s] = row[ic];
             }
         }
+        // this lane's reference exponents of the ready {b, c} weights (re-read per a:
+        // not live across the walk; consumed late in the prologue)
+        int2 bref = make_int2(0, 0);
+        if (SEP) bref = A.bcrn[(size_t)tile * 64 + t];
         wave_lds_order();  // previous a's (a, b) terms and slots fully consumed
         if (A.trace && ai == 0) t_fn[0] = wall_clock64();
         // this lane's {b} and {c} weights: registers (SEP), or re-read from LDS
@@ -1108,6 +1117,17 @@ __device__ __forceinline__ void sweep3_unit_fast(const Sweep3Args& A, int unit, 
         // reference could not carry a large extension: redone (robust)
         wide |= __builtin_amdgcn_ballot_w64((pMu[0] != 0.0 && pN[0] - Ru[0] < -kMaxRefGap) ||
                                             (pMu[1] != 0.0 && pN[1] - Ru[1] < -kMaxRefGap)) != 0;
+        // The ready {b, c} weights r_s sit at the lane's own reference 2^ref_s; the walk
+        // wants them relative to 2^Ru_s: one lane constant kap_s = 2^(ref_s - Ru_s)
+        // per a (SEP units).  The multiply is not issued per step: kap_s folds into
+        // what v_s[{b, c}] meets (the one-study vectors below, Z1's inner FMA, four
+        // ZS entries after the walk).  ref_s - Ru_s beyond kMaxRefGap: some b of
+        // the block gives a set with n_abc - Ru that large (n_abc >= n_bc up to pivot
+        // factors), the case the robust variant is for; kap is clamped so it stays
+        // finite.  Far below, kap underflows to 0 as the per-step ldexp did.
+        const int kg0 = bref.x - Ru[0], kg1 = bref.y - Ru[1];
+        if (sep) wide |= __builtin_amdgcn_ballot_w64(max(kg0, kg1) > kMaxRefGap) != 0;
+        const double kap[2] = {ldexp(1.0, min(kg0, kMaxRefGap)), ldexp(1.0, min(kg1, kMaxRefGap))};
         // the previous a's record: its sums at the wave's largest shift
         const int rGw = mx[1], rdg = rG != EMPTY ? rG - rGw : -2000;
         double abS[2] = {0.0, 0.0};  // sum over the slots of the {a, b} weights, at 2^abM
@@ -1205,6 +1225,12 @@ __device__ __forceinline__ void sweep3_unit_fast(const Sweep3Args& A, int unit, 
             for (int s = 0; s < 2; s++)
 #pragma unroll
                 for (int i = 2; i < 4; i++) uL[s][i] *= fW[s];
+            // v_s[{b, c}] = kap_s r_s meets uW_(1 - s)[2] and uL_(1 - s)[2] only
+#pragma unroll
+            for (int s = 0; s < 2; s++) {
+                uW[1 - s][2] *= kap[s];
+                uL[1 - s][2] *= kap[s];
+            }
         } else {
 #pragma unroll
             for (int i = 0; i < 4; i++) {
@@ -1285,18 +1311,19 @@ __device__ __forceinline__ void sweep3_unit_fast(const Sweep3Args& A, int unit, 
             auto acc = [&](double (&arr)[64]) -> double* { return reinterpret_cast<double*>(reinterpret_cast<char*>(arr) + o8); };
             const double2 aMuB = ft.muB, aMu = ft.mu;
             // v[s][A] = E_s[A + b] relative to 2^{Ru_s}: {b}, {a, b}, {b, c}, {a, b, c}
+            // (SEP: v[s][2] is the ready weight r_s, relative to 2^ref_s: its kap_s
+            // rides in uW / uL, in Z1 and, after the walk, in ZS)
             double v[2][4];
             int d3s = ft.e;
 #pragma unroll
             for (int s = 0; s < 2; s++) {
                 const int d3 = N[s] >> 8;  // c's extension exponent: n3 - n_ab (within one bit)
                 const double mu3 = (s ? ft.tb1 : ft.tb0) * q[s] * (s ? aMu.y : aMu.x);
-                const int n2 = s ? ncur.y : ncur.x;
-                const double mu2 = s ? mcur.y : mcur.x;
+                const double r2 = s ? mcur.y : mcur.x;
                 d3s += d3;
                 v[s][0] = s ? aMuB.y : aMuB.x;
                 v[s][1] = s ? aMu.y : aMu.x;
-                v[s][2] = ldexp(mu2, n2 - Ru[s]);
+                v[s][2] = sepc ? r2 : ldexp(r2, (s ? ncur.y : ncur.x) - Ru[s]);
                 v[s][3] = ldexp(mu3, d3);
             }
             dA = max(dA, d3s);
@@ -1323,7 +1350,8 @@ __device__ __forceinline__ void sweep3_unit_fast(const Sweep3Args& A, int unit, 
             const double Z0 = sepc ? fma(v[0][0], v[1][3], v[0][3] * v[1][0])
                                    : fma(v[0][0], v[1][3], fma(v[0][2], v[1][1], fma(v[0][1], v[1][2], v[0][3] * v[1][0])));
             // Z1: one of a, c in both studies -> (3,1), (1,3), (3,2), (2,3)
-            const double Z1 = fma(v[0][2], v[1][3], fma(v[0][3], v[1][2], fma(v[0][1], v[1][3], v[0][3] * v[1][1])));
+            const double Z1 = sepc ? fma(v[1][3], fma(kap[0], v[0][2], v[0][1]), v[0][3] * fma(kap[1], v[1][2], v[1][1]))
+                                   : fma(v[0][2], v[1][3], fma(v[0][3], v[1][2], fma(v[0][1], v[1][3], v[0][3] * v[1][1])));
             const double z22 = v[0][3] * v[1][3];
             const double WB2 = fma(rho, fma(rho, z22, Z1), Z0);
             const double LB2 = (Z0 + Z1) + z22;
@@ -1366,12 +1394,12 @@ __device__ __forceinline__ void sweep3_unit_fast(const Sweep3Args& A, int unit, 
             // (the tile bases are wave-uniform and the lane's row offset a 32-bit
             // unsigned byte count: base + offset + row immediates, one add per pair)
             const char* gb = (const char*)(A.g01 + (size_t)tile * 4096);
-            const char* mb = (const char*)(A.mu01 + (size_t)tile * 4096);
-            const char* nb = (const char*)(A.bcn + (size_t)tile * 4096);
+            const char* mb = (const char*)((SEP ? A.bcr : A.mu01) + (size_t)tile * 4096);
+            const char* nb = (const char*)(A.bcn + (size_t)tile * 4096);  // (read by non-SEP units only)
             unsigned o16 = (unsigned)(j0 * 64 + t) * 16u, o8 = o16 >> 1;  // double2 / int2 rows: 1024 / 512 bytes
             double2 g_next = *(const double2*)(gb + o16 + 1024);
             double2 m_cur = mnx;
-            int2 n_cur = nnx;
+            int2 n_cur = nnx, n_nxt = make_int2(0, 0);
             int NA[2], NB[2];
             double qA[2], qB[2];
             unsigned s8 = o16of(j0) >> 1;  // step j's slot offset (8-byte arrays)
@@ -1385,7 +1413,7 @@ __device__ __forceinline__ void sweep3_unit_fast(const Sweep3Args& A, int unit, 
                 o16 += 2048u;
                 o8 += 1024u;
                 double2 m_nxt = *(const double2*)(mb + o16 - 1024);
-                int2 n_nxt = *(const int2*)(nb + o8 - 512);
+                if (!SEP) n_nxt = *(const int2*)(nb + o8 - 512);
                 double2 g_after = *(const double2*)(gb + o16);
                 const unsigned s8b = (s8 + 8u) & 504u;
                 chain(s8b << 1, g_next, NB, qB);
@@ -1396,7 +1424,7 @@ __device__ __forceinline__ void sweep3_unit_fast(const Sweep3Args& A, int unit, 
                 // one wave and LDS executes a wave's instructions in issue order
                 __builtin_amdgcn_wave_barrier();
                 m_cur = *(const double2*)(mb + o16);
-                n_cur = *(const int2*)(nb + o8);
+                if (!SEP) n_cur = *(const int2*)(nb + o8);
                 g_next = *(const double2*)(gb + o16 + 1024);
                 // the row loads at the top of this pair of steps are first used here
                 // (and this half's loads first in the next pair): pinned, so the
@@ -1404,14 +1432,14 @@ __device__ __forceinline__ void sweep3_unit_fast(const Sweep3Args& A, int unit, 
                 // issued only ~80 instructions earlier (the tile rows come from the
                 // MALL).  Same-box A/B: world 1 1.043 -> 1.016 ms.
                 pin_vgpr(m_nxt);
-                pin_vgpr(n_nxt);
+                if (!SEP) pin_vgpr(n_nxt);
                 pin_vgpr(g_after);
                 chain(s8 << 1, g_after, NA, qA);  // (the last pair's is not used)
                 finish_ft(s8b, ftB, NB, qB, m_nxt, n_nxt);
                 ftA = ld_ft(s8 << 1, NA);
                 __builtin_amdgcn_wave_barrier();
                 pin_vgpr(m_cur);
-                pin_vgpr(n_cur);
+                if (!SEP) pin_vgpr(n_cur);
                 pin_vgpr(g_next);
             }
         };
@@ -1423,7 +1451,7 @@ __device__ __forceinline__ void sweep3_unit_fast(const Sweep3Args& A, int unit, 
                 nnx = bnn[je * 64];
             }
         }
-        for (int j = je; j < j1; j++) {
+        for (int j = je; j < j1; j++) {  // (never in SEP units: their walk is all pipelined)
             const double2 gcur = gnx, mcur = mnx;
             const int2 ncur = nnx;
             if (j + 1 < j1) {
@@ -1463,6 +1491,15 @@ __device__ __forceinline__ void sweep3_unit_fast(const Sweep3Args& A, int unit, 
             for (int i = sep ? 3 : 0; i < 4; i++) {
                 V0[i] *= m0f;
                 V1[i] *= m1f;
+            }
+            // SEP: the four ZS entries whose pair holds a {b, c} weight summed r_s
+            // unscaled: (i0, i1) = (2, 1), (2, 3) take kap_0; (1, 2), (3, 2) kap_1
+            // (before l01, as the per-step products carried it: no new overflow)
+            if (sep) {
+                ZS[1][0] *= kap[0];
+                ZS[1][2] *= kap[0];
+                ZS[0][1] *= kap[1];
+                ZS[0][2] *= kap[1];
             }
             const double l01 = m0f * m1f;
 #pragma unroll
@@ -1642,7 +1679,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PSX_K3_WAVES
     // each copy's walk loop gets its own register assignment (one function with
     // both loops rotated ~14 loop-carried registers per step pair in the other)
     const int4 un = units[blockIdx.x];
-    if ((un.z & 0xffff) != (un.w & 0xffff) && (un.z >> 16) == 0 && (un.w >> 16) == 64)
+    // a tile whose {b, c} weights do not fit the ready form (k_bc3_ready): robust
+    const int uK = un.z & 0xffff, uC = un.w & 0xffff;
+    if (A.bcwide[uC * (uC + 1) / 2 + uK])
+        redo = true;
+    else if (uK != uC && (un.z >> 16) == 0 && (un.w >> 16) == 64)
         sweep3_unit_fast<ALLPRES, true>(A, blockIdx.x, units, rec, srec, rec_stride, flag, pos, sm, redo);
     else
         sweep3_unit_fast<ALLPRES, false>(A, blockIdx.x, units, rec, srec, rec_stride, flag, pos, sm, redo);
@@ -1700,6 +1741,67 @@ __global__ __launch_bounds__(64) void k_bc3_rowsum(const double2* __restrict__ m
     }
     sm[(size_t)blockIdx.x * 64 + threadIdx.x] = make_double2(S0, S1);
     sn[(size_t)blockIdx.x * 64 + threadIdx.x] = make_int2(M0, M1);
+}
+
+// The fast walk's ready {b, c} weights: bcr[tile][j][t] = mu01 * 2^(bcn - ref), both
+// studies, for the off-diagonal (SEP) units, with ref_s[tile][t] the largest binade (bcn + ilogb(mu01)) among lane
+// t's finite non-zero weights of the tile, so the lane's largest entry lies in
+// [1, 2) and the walk needs one scale 2^(ref_s - Ru_s) per lane and a instead of
+// one ldexp per step.  A power-of-two scaling: exact while the entry stays
+// normal.  (A folded diagonal tile is walked on steps 1 .. 32 only; its other
+// steps, step 0 pairing a SNP with itself, take no part in the reference.)
+//
+// Range.  A plain double holds ~1,022 binades under the reference.  A tile in
+// which some lane's non-zero weights span more than kMaxBcSpan = 900 binades is
+// marked wide, and every unit of it runs the robust variant (which reads mu01 /
+// bcn): no entry the fast walk reads is ever flushed, and each is a normal
+// number with 122 binades to spare for the pivot factors the walk multiplies it
+// with.  What the walk can still lose is a product r_s x (a slot weight) that
+// underflows before kap_s is applied; such a product is below 2^-900 of the
+// lane's largest {b, c} weight times the same slot scale, the bound the uniform
+// slot shift already accepts for terms counted in the same totals.
+constexpr int kMaxBcSpan = 900;
+__global__ __launch_bounds__(64) void k_bc3_ready(const double2* __restrict__ mu01, const int2* __restrict__ n,
+                                                  double2* __restrict__ bcr, int2* __restrict__ bcrn,
+                                                  int* __restrict__ bcwide) {
+    const int tile = blockIdx.x;
+    const size_t base = (size_t)tile * 4096 + threadIdx.x;
+    int C = 0;
+    while ((C + 1) * (C + 2) / 2 <= tile) C++;
+    // the steps some walk takes: all 64 of an off-diagonal tile, 1 .. 32 of a folded diagonal one
+    const bool diag = tile - C * (C + 1) / 2 == C;
+    const int jb = diag ? 1 : 0, je = diag ? 33 : 64;
+    int M0 = EMPTY, M1 = EMPTY, L0 = -EMPTY, L1 = -EMPTY;
+    for (int j = jb; j < je; j++) {
+        const double2 m = mu01[base + 64 * j];
+        const int2 e = n[base + 64 * j];
+        if (m.x > 0.0 && m.x < HUGE_VAL) {
+            const int b = e.x + ilogb(m.x);
+            M0 = max(M0, b);
+            L0 = min(L0, b);
+        }
+        if (m.y > 0.0 && m.y < HUGE_VAL) {
+            const int b = e.y + ilogb(m.y);
+            M1 = max(M1, b);
+            L1 = min(L1, b);
+        }
+    }
+    for (int j = 0; j < 64; j++) {
+        const double2 m = mu01[base + 64 * j];
+        const int2 e = n[base + 64 * j];
+        bcr[base + 64 * j] = make_double2(ldexp(m.x, e.x - M0), ldexp(m.y, e.y - M1));
+    }
+    bcrn[(size_t)tile * 64 + threadIdx.x] = make_int2(M0, M1);
+    // (diagonal tiles' units do not read bcr: never wide)
+    const bool w = !diag && ((M0 != EMPTY && M0 - L0 > kMaxBcSpan) || (M1 != EMPTY && M1 - L1 > kMaxBcSpan));
+    const bool any = __builtin_amdgcn_ballot_w64(w) != 0;
+    if (threadIdx.x == 0) bcwide[tile] = any ? 1 : 0;
+}
+
+int launch_bc3_ready(int ntile, const double2* mu01, const int2* n, double2* bcr, int2* bcrn, int* bcwide,
+                     hipStream_t st) {
+    hipLaunchKernelGGL(k_bc3_ready, dim3(ntile), dim3(64), 0, st, mu01, n, bcr, bcrn, bcwide);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 int launch_bc3_rowsum(int ntile, const double2* mu01, const int2* n, double2* sm, int2* sn, hipStream_t st) {
