@@ -1116,15 +1116,24 @@ int ensure(T*& p, size_t& cap, size_t n) {
 
 // pinned host buffer of at least n elements (contents not preserved)
 template <typename T>
-int ensure_host(T*& p, size_t& cap, size_t n) {
+int ensure_host(T*& p, size_t& cap, size_t n, hipError_t (*alloc)(void**, size_t) = psx::hmalloc_raw) {
     if (n <= cap) return 0;
     const size_t nc = std::max(n, cap * 2);
     if (p) psx::hfree(p);
     p = nullptr;
     cap = 0;
-    HIPCHK(psx::hmalloc(reinterpret_cast<void**>(&p), nc * sizeof(T)));
+    HIPCHK(alloc(reinterpret_cast<void**>(&p), nc * sizeof(T)));
     cap = nc;
     return 0;
+}
+
+// the same in coherent pinned memory (device -> host hand-offs), zero-filled when grown
+template <typename T>
+int ensure_host_coherent(T*& p, size_t& cap, size_t n) {
+    if (n <= cap) return 0;
+    const int rc = ensure_host(p, cap, n, psx::hmalloc_coherent_raw);
+    if (rc == 0) std::memset(p, 0, cap * sizeof(T));
+    return rc;
 }
 
 double logval(const psx_engine* e, int32_t m, double s) {
@@ -2652,7 +2661,14 @@ int psx_run_configs(psx_engine* e, const int16_t* rows, int64_t n_rows, int32_t 
 extern "C" __device__ __attribute__((const)) int __ockl_wfred_add_i32(int);
 
 namespace {
-constexpr int kKeyBits = 21;  // a sorted set of <= 6 as two words of three (index + 1) fields
+using psx::kKeyBits;
+using psx::mix64;
+using psx::SssGeom;
+using psx::kUnseen;
+using psx::kNulls;
+using psx::kCurPos;
+using psx::kCurNull;
+using psx::kNCnt;
 constexpr int kKeyMaxU = (1 << kKeyBits) - 2;
 
 struct MapEntry {
@@ -2661,13 +2677,6 @@ struct MapEntry {
     int state, pad;
 };
 
-__host__ __device__ inline unsigned long long mix64(unsigned long long x) {
-    x ^= x >> 30;
-    x *= 0xbf58476d1ce4e5b9ULL;
-    x ^= x >> 27;
-    x *= 0x94d049bb133111ebULL;
-    return x ^ (x >> 31);
-}
 __device__ inline unsigned long long map_slot(unsigned long long lo, unsigned long long hi, unsigned long long mask) {
     return mix64(lo ^ mix64(hi + 0x9e3779b97f4a7c15ULL)) & mask;
 }
@@ -2722,7 +2731,8 @@ struct SssIter {
 };
 
 // neighbour i (0 .. n_nbd) or, for i == -1, the current configuration: its
-// sorted members (-1 padded to `stride`) and size
+// sorted members (-1 padded to `stride`) and size.  (The host's statement of
+// the same order, pinned on the CPU, is psx::sss_neighbour.)
 __device__ int nbd_row(const SssIter& it, int i, int* row) {
     const int k = it.k;
     int x = -1, skip = -1, n;
@@ -2758,13 +2768,6 @@ __device__ int nbd_row(const SssIter& it, int i, int* row) {
     for (int j = m; j < it.stride; j++) row[j] = -1;
     return n;
 }
-
-// iteration counters: k_sss_eval's block 0 writes the current configuration's
-// two (kCurPos: 0 if it is evaluated, else -1; kCurNull: 1 if it is an unseen
-// null configuration), k_sss_post's scalar block counts the unseen neighbours
-// and null configurations from mark[] (no contended atomics in the eval) and
-// copies all four to pinned host memory
-enum { kUnseen = 0, kNulls = 1, kCurPos = 2, kCurNull = 3, kNCnt = 4 };
 
 // item p of the iteration: the current configuration (p = 0, always evaluated
 // when unseen: sss_postcal.cpp:195-202) or neighbour i = p - 1.  mark[i]: -1
@@ -3063,185 +3066,241 @@ __global__ void k_sss_unpack(const double* __restrict__ rcv, int world, int n_it
     }
 }
 
-struct SssDev {
-    MapEntry* T = nullptr;
-    size_t cap = 0, used = 0;
-    size_t nmax = 0, nmax_full = 0;  // item capacity of the per-item arrays (full / hscore)
-    // (start, stop) event pairs around the evals, read kRingE iterations later
-    // (by then complete) instead of once per iteration
+int launch_map_rehash(const MapEntry* old, size_t n, MapEntry* T, unsigned long long mask, hipStream_t st) {
+    hipLaunchKernelGGL(k_map_rehash, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, old, n, T, mask);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// The evals' device time, sampled: (start, stop) event pairs in a ring, read
+// kRingE iterations later (by then complete) instead of once per iteration.
+// Plain event records around the eval: hipExtLaunchKernelGGL's in-packet events
+// cost the host ~12 us more per launch here (profiles/archive/r03i_sss_host_phases.txt).
+// The start event only on every kEvEvery-th iteration (an event record is
+// ~1-2 us of host time): the eval time is sampled there and scaled to all
+// iterations.
+struct EvalTimer {
     static constexpr int kRingE = 8;
-    static constexpr int kEvEvery = 4;  // start events on every 4th iteration (kRingE a multiple)
-    hipEvent_t ev[2 * kRingE] = {};
+    static constexpr int kEvEvery = 4;  // (kRingE a multiple)
+    hipEvent_t* ev;                     // 2 * kRingE events
+    hipStream_t stream;
+    double ms = 0;
+    int samples = 0;
+    hipEvent_t stop(int iter) const { return ev[2 * (iter % kRingE) + 1]; }
+    int take(int q) {  // the pair of iteration q, a sampled one
+        float t = 0;
+        HIPCHK(hipEventElapsedTime(&t, ev[2 * (q % kRingE)], stop(q)));
+        ms += t;
+        samples++;
+        return 0;
+    }
+    // before iteration iter's eval launch
+    int begin(int iter) {
+        int rc;
+        if (iter >= kRingE && (iter - kRingE) % kEvEvery == 0 && (rc = take(iter - kRingE))) return rc;
+        if (iter % kEvEvery == 0) HIPCHK(hipEventRecord(ev[2 * (iter % kRingE)], stream));
+        return 0;
+    }
+    // after it: the stop event, where the eval is sampled or the host waits on stop(iter)
+    int end(int iter, bool host_waits) {
+        if (iter % kEvEvery == 0 || host_waits) HIPCHK(hipEventRecord(stop(iter), stream));
+        return 0;
+    }
+    // after the last of `ran` iterations has completed: the pairs still in the
+    // ring, and the sampled evals' mean over every iteration
+    int finish(int ran, double& kernel_ms) {
+        int rc;
+        for (int q = std::max(0, ran - kRingE); q < ran; q++)
+            if (q % kEvEvery == 0 && (rc = take(q))) return rc;
+        if (samples) ms *= (double)ran / samples;
+        kernel_ms = ms;
+        return 0;
+    }
+};
+
+// the walk's workspace, kept across walks (every buffer grown, never shrunk)
+struct SssDev {
+    MapEntry* T = nullptr;            // the set map of the narrow walk ...
+    psx::WideMapEntry* TW = nullptr;  // ... and of the wide one (max_causal 7 .. 10)
+    size_t cap = 0, cap_w = 0;        // their slots (powers of two)
+    size_t used = 0;                  // sets in the running walk's map
+    hipEvent_t ev[2 * EvalTimer::kRingE] = {};
     int* rows = nullptr;      // per item: its set (evaluated items)
     int* mark = nullptr;      // per neighbour: -1 seen, -2 unseen null, else its item
     int* cnt = nullptr;
     double* full = nullptr;   // per item: every rank's scores (world > 1)
-    double* lk = nullptr;     // pinned host: every neighbour's score
+    double* lk = nullptr;     // coherent pinned host: every neighbour's score
     SetRec* shost = nullptr;  // pinned host: the scalars after the iteration
     int* hcnt = nullptr;      // pinned host: the counters
-    unsigned long long* hmark = nullptr;  // pinned host: per neighbour, its mark word (one rank)
+    unsigned long long* hmark = nullptr;  // coherent pinned host: per neighbour, its mark word (narrow walk, one rank)
     unsigned long long* trace = nullptr;  // PSX_SSS_TRACE: item 1's eval phase clocks (pinned host)
     double* hscore = nullptr; // pinned host: gathered item scores (world > 1)
     double* dx = nullptr;     // device exchange: send block | receive blocks (world > 1)
-    size_t cap_dx = 0;
     double* hnorm = nullptr;  // pinned host: every rank's normaliser (m, s) (device exchange)
-    int cap_hnorm = 0;
+    unsigned long long* keys = nullptr;  // wide walk, per neighbour: its packed set (four words)
+    int* hmk = nullptr;                  // wide walk, pinned host: per neighbour, its mark
+    size_t cap_rows = 0, cap_mark = 0, cap_cnt = 0, cap_full = 0, cap_lk = 0, cap_shost = 0, cap_hcnt = 0,
+           cap_hmark = 0, cap_trace = 0, cap_hscore = 0, cap_dx = 0, cap_hnorm = 0, cap_keys = 0, cap_hmk = 0;
     unsigned int seq = 0;     // the last iteration tag of the mark words (never 0)
-    // the wide walk (max_causal 7 .. 10, run_sss_wide): its own map and per-neighbour keys / host marks
-    psx::WideMapEntry* TW = nullptr;
-    size_t cap_w = 0, nmax_w = 0;
-    unsigned long long* keys = nullptr;  // per neighbour: its packed set (four words)
-    int* hmk = nullptr;                  // pinned host: per neighbour, its mark
     ~SssDev() {
         psx::dfree(T);
         psx::dfree(TW);
-        psx::dfree(keys);
-        if (hmk) psx::hfree(hmk);
         psx::dfree(rows);
         psx::dfree(mark);
         psx::dfree(cnt);
         psx::dfree(full);
-        if (lk) psx::hfree(lk);
-        if (shost) psx::hfree(shost);
-        if (hcnt) psx::hfree(hcnt);
-        if (hmark) psx::hfree(hmark);
-        if (hscore) psx::hfree(hscore);
-        if (trace) psx::hfree(trace);
         psx::dfree(dx);
-        if (hnorm) psx::hfree(hnorm);
-        for (int i = 0; i < 2 * kRingE; i++)
-            if (ev[i]) hipEventDestroy(ev[i]);
+        psx::dfree(keys);
+        psx::hfree(lk);
+        psx::hfree(shost);
+        psx::hfree(hcnt);
+        psx::hfree(hmark);
+        psx::hfree(trace);
+        psx::hfree(hscore);
+        psx::hfree(hnorm);
+        psx::hfree(hmk);
+        for (hipEvent_t x : ev)
+            if (x) hipEventDestroy(x);
     }
 };
 
 void sss_release(SssDev* d) { delete d; }
 
-// the walk's workspace for up to nmax items per iteration (grown, never shrunk;
-// the map is cleared for every walk); wide: the wide walk's map and keys
-// instead of the narrow map
-int sss_workspace(psx_engine* e, size_t nmax, int world, hipStream_t s, bool wide = false) {
-    if (!e->sss) e->sss = new SssDev();
-    SssDev& D = *e->sss;
-    if (!D.cnt) {
-        for (int i = 0; i < 2 * SssDev::kRingE; i++) HIPCHK(hipEventCreate(&D.ev[i]));
-        HIPCHK(psx::dmalloc(&D.cnt, kNCnt * sizeof(int)));
-        HIPCHK(psx::hmalloc(reinterpret_cast<void**>(&D.shost), sizeof(SetRec)));
-        HIPCHK(psx::hmalloc(reinterpret_cast<void**>(&D.hcnt), kNCnt * sizeof(int)));
-        if (std::getenv("PSX_SSS_TRACE")) {
-            HIPCHK(psx::hmalloc(reinterpret_cast<void**>(&D.trace), 8 * sizeof(unsigned long long)));
-            std::memset(D.trace, 0, 8 * sizeof(unsigned long long));
-        }
-    }
-    if (D.nmax < nmax) {
-        psx::dfree(D.rows); psx::dfree(D.mark);
-        if (D.lk) psx::hfree(D.lk);
-        if (D.hmark) psx::hfree(D.hmark);
-        D.rows = D.mark = nullptr;
-        D.hmark = nullptr;
-        D.lk = nullptr;
-        HIPCHK(psx::dmalloc(&D.rows, nmax * PSX_KMAX * sizeof(int)));
-        HIPCHK(psx::dmalloc(&D.mark, nmax * sizeof(int)));
-        // coherent: the eval's weight / mark-word hand-off (publish_mark) relies on
-        // device stores reaching host memory in acknowledgement order
-        HIPCHK(psx::hmalloc_coherent_raw(reinterpret_cast<void**>(&D.lk), nmax * sizeof(double)));
-        HIPCHK(psx::hmalloc_coherent_raw(reinterpret_cast<void**>(&D.hmark), nmax * sizeof(unsigned long long)));
-        std::memset(D.hmark, 0, nmax * sizeof(unsigned long long));  // tag 0: no iteration
-        D.nmax = nmax;
-    }
-    if (world > 1 && D.nmax_full < nmax) {
-        psx::dfree(D.full);
-        if (D.hscore) psx::hfree(D.hscore);
-        D.full = nullptr;
-        D.hscore = nullptr;
-        HIPCHK(psx::dmalloc(&D.full, nmax * sizeof(double)));
-        HIPCHK(psx::hmalloc(reinterpret_cast<void**>(&D.hscore), nmax * sizeof(double)));
-        D.nmax_full = nmax;
-    }
-    size_t cap = 1 << 16;
-    while (cap < 4 * nmax) cap <<= 1;
-    if (wide) {
-        if (D.nmax_w < nmax) {
-            psx::dfree(D.keys);
-            if (D.hmk) psx::hfree(D.hmk);
-            D.keys = nullptr;
-            D.hmk = nullptr;
-            D.nmax_w = 0;
-            HIPCHK(psx::dmalloc(&D.keys, nmax * 4 * sizeof(unsigned long long)));
-            HIPCHK(psx::hmalloc(&D.hmk, nmax * sizeof(int)));
-            D.nmax_w = nmax;
-        }
-        if (D.cap_w < cap) {
-            psx::dfree(D.TW);
-            D.TW = nullptr;
-            D.cap_w = 0;
-            HIPCHK(psx::dmalloc(&D.TW, cap * sizeof(psx::WideMapEntry)));
-            D.cap_w = cap;
-        }
-        HIPCHK(hipMemsetAsync(D.TW, 0, D.cap_w * sizeof(psx::WideMapEntry), s));
-        D.used = 0;
-        return 0;
-    }
-    if (D.cap < cap) {
-        psx::dfree(D.T);
-        D.T = nullptr;
-        HIPCHK(psx::dmalloc(&D.T, cap * sizeof(MapEntry)));
-        D.cap = cap;
-    }
-    HIPCHK(hipMemsetAsync(D.T, 0, D.cap * sizeof(MapEntry), s));
-    D.used = 0;
+extern "C++" {  // (templates, inside the ABI's extern "C" block)
+// a walk's map for up to nmax items per iteration, cleared (it is grown, at load > 1/2, by grow_map)
+template <class Entry>
+int reset_map(Entry*& T, size_t& cap, size_t nmax, hipStream_t s) {
+    size_t want = 1 << 16;
+    while (want < 4 * nmax) want <<= 1;
+    const int rc = ensure(T, cap, want);  // (a power of two stays one under ensure's doubling)
+    if (rc) return rc;
+    HIPCHK(hipMemsetAsync(T, 0, cap * sizeof(Entry), s));
     return 0;
 }
 
-// The next configuration: one neighbour drawn from every neighbour's score
-// lk[0 .. n_nbd) (swap ++ minus ++ plus) with the reference's draws in the
-// reference's order (sss_postcal.cpp:296-343), put in cur[0 .. k) (ascending).
-void sss_sample_next(const double* lk, int num_zero, int num_minus, int num_plus, std::mt19937& gen,
-                     std::vector<double>& pr, int* cur, int& k) {
-    const int n_nbd = num_zero + num_minus + num_plus;
-    double wz = 0, wm = 0, wp = 0;
-    size_t zs = n_nbd, ms = n_nbd, ps = n_nbd;
-    // each group: discrete_distribution(exp(lk - max))(gen) and the weights'
-    // sum (accumulate), the draw restated without the distribution's vectors
-    // (psx_sample.h: bit-identical partial sums, the same index)
-    auto group = [&](int b, int en, double& wsum, size_t& smp) {
-        pr.resize((size_t)(en - b));
-        double mx = *std::max_element(lk + b, lk + en);
-        // (slicing these exps over spinning host threads measured slower: the
-        // serial loop takes ~5 us at 1,000 neighbours, profiles/archive/r03v_sss_threads.txt)
-        double s = 0.0;
-        for (int ii = b; ii < en; ii++) s += (pr[ii - b] = std::exp(lk[ii] - mx));
-        smp = psx::discrete_draw(pr.data(), pr.size(), s, gen);
-        wsum = s;
-    };
-    if (num_zero != 0) group(0, num_zero, wz, zs);                               // :296-306
-    if (num_minus != 0) group(num_zero, num_zero + num_minus, wm, ms);           // :307-317
-    if (num_plus != 0) group(num_zero + num_minus, n_nbd, wp, ps);               // :318-328
-    const double w3[3] = {wz, wm, wp};                                           // :330-343
-    size_t idx = psx::discrete_draw(w3, 3, (0.0 + wz + wm) + wp, gen), fin = 0;
-    switch (idx) {
-        case 0: fin = zs; break;
-        case 1: fin = ms + num_zero; break;
-        case 2: fin = ps + num_zero + num_minus; break;
+// The map stays at load <= 1/2 (every neighbour may be new): before an
+// iteration of n_nbd neighbours, the map of `used` sets at the capacity that
+// holds them all, every entry re-inserted.
+template <class Entry>
+int grow_map(Entry*& T, size_t& cap, size_t used, int n_nbd,
+             int (*rehash)(const Entry*, size_t, Entry*, unsigned long long, hipStream_t), hipStream_t s) {
+    const size_t need = 2 * (used + (size_t)n_nbd + 1);
+    if (need <= cap) return 0;
+    size_t nc = cap;
+    while (need > nc) nc <<= 1;
+    Entry* nt = nullptr;
+    HIPCHK(psx::dmalloc(&nt, nc * sizeof(Entry)));
+    hipError_t err = hipMemsetAsync(nt, 0, nc * sizeof(Entry), s);
+    const bool launched = err == hipSuccess && rehash(T, cap, nt, (unsigned long long)(nc - 1), s) == 0;
+    if (launched) err = hipStreamSynchronize(s);
+    if (!launched || err != hipSuccess) {
+        psx::dfree(nt);
+        return fail(PSX_EHIP, std::string("SSS map growth failed: ") +
+                                  (err != hipSuccess ? hipGetErrorString(err) : "the rehash launch"));
     }
-    // the chosen neighbour becomes the current configuration (host copy of nbd_row)
-    const int i = (int)fin;
-    int x = -1, skip = -1, n;
-    if (i < num_zero) { skip = i % k; x = i / k; n = k; }
-    else if (i < num_zero + num_minus) { skip = i - num_zero; n = k - 1; }
-    else { x = i - num_zero - num_minus; n = k + 1; }
-    if (x >= 0)
-        for (int j = 0; j < k; j++)
-            if (cur[j] <= x) x++;
-    int nxt[PSX_KWIDE], m = 0;
-    bool put = x < 0;
-    for (int j = 0; j < k; j++) {
-        if (j == skip) continue;
-        if (!put && x < cur[j]) { nxt[m++] = x; put = true; }
-        nxt[m++] = cur[j];
+    psx::dfree(T);
+    T = nt;
+    cap = nc;
+    return 0;
+}
+
+// the fields the walks' device argument structs share (SssIter, psx::SssWideIter)
+template <class It>
+void sss_iter_fill(It& it, const int* cur, int k, const psx_engine* e, const SssGeom& g) {
+    for (int j = 0; j < (int)std::size(it.cur); j++) it.cur[j] = j < k ? cur[j] : -1;
+    it.k = k;
+    it.U = e->U;
+    it.stride = std::max(e->maxc, 1);
+    it.num_zero = g.num_zero;
+    it.num_minus = g.num_minus;
+    it.num_plus = g.num_plus;
+    it.n_nbd = g.n_nbd;
+    it.null_score = e->K + e->L0;
+}
+}  // extern "C++"
+
+// The walk's workspace for this engine's (U, max_causal), and its map cleared;
+// wide: the wide walk's map, keys and marks instead of the narrow map.
+int sss_workspace(psx_engine* e, int world, bool wide) {
+    const bool created = !e->sss;
+    if (created) e->sss = new SssDev();
+    SssDev& D = *e->sss;
+    const int U = e->U, C = e->maxc;
+    // the most items of an iteration: the current configuration + the largest
+    // neighbourhood (k = C: swaps C (U - C), minus C; k < C: + U - k plus sets)
+    const size_t nmax = (size_t)C * U + C + U + 2;
+    int rc;
+    for (hipEvent_t& x : D.ev)
+        if (!x) HIPCHK(hipEventCreate(&x));
+    if (created && std::getenv("PSX_SSS_TRACE")) {
+        if ((rc = ensure_host(D.trace, D.cap_trace, 8))) return rc;
+        std::memset(D.trace, 0, 8 * sizeof(unsigned long long));
     }
-    if (!put) nxt[m++] = x;
-    std::copy(nxt, nxt + n, cur);
-    k = n;
+    if ((rc = ensure(D.cnt, D.cap_cnt, kNCnt))) return rc;
+    if ((rc = ensure_host(D.shost, D.cap_shost, 1))) return rc;
+    if ((rc = ensure_host(D.hcnt, D.cap_hcnt, kNCnt))) return rc;
+    if ((rc = ensure(D.rows, D.cap_rows, nmax * PSX_KMAX))) return rc;
+    if ((rc = ensure(D.mark, D.cap_mark, nmax))) return rc;
+    // coherent: the eval's weight / mark-word hand-off (publish_mark) relies on
+    // device stores reaching host memory in acknowledgement order; a fresh mark
+    // word is 0, the tag of no iteration
+    if ((rc = ensure_host_coherent(D.lk, D.cap_lk, nmax))) return rc;
+    if ((rc = ensure_host_coherent(D.hmark, D.cap_hmark, nmax))) return rc;
+    if (world > 1) {
+        if ((rc = ensure(D.full, D.cap_full, nmax))) return rc;
+        if ((rc = ensure_host(D.hscore, D.cap_hscore, nmax))) return rc;
+    }
+    if ((rc = ensure(e->dsrec, e->cap_srec, nmax))) return rc;
+    if ((rc = ensure(e->dmrec, e->cap_mrec, nmax * std::max(C, 1)))) return rc;
+    if ((rc = ensure(e->dscore, e->cap_score, nmax))) return rc;
+    D.used = 0;
+    if (!wide) return reset_map(D.T, D.cap, nmax, e->stream);
+    if ((rc = ensure(D.keys, D.cap_keys, nmax * 4))) return rc;
+    if ((rc = ensure_host(D.hmk, D.cap_hmk, nmax))) return rc;
+    return reset_map(D.TW, D.cap_w, nmax, e->stream);
+}
+
+// The ranks' normalisers (m, s), rank r's at parts[r * stride], combined in rank order.
+double combine_norms(const psx_engine* e, const double* parts, size_t stride, int world) {
+    double mx = -INFINITY;
+    std::vector<double> part(world, 0.0);
+    for (int r = 0; r < world; r++) {
+        part[r] = logval(e, (int32_t)parts[r * stride], parts[r * stride + 1]);
+        if (part[r] != 0.0) mx = std::max(mx, part[r]);
+    }
+    double acc = 0.0;
+    for (int r = 0; r < world; r++)
+        if (part[r] != 0.0) acc += std::exp(part[r] - mx);
+    return acc > 0 ? mx + std::log(acc) : 0.0;
+}
+
+// One rank: the iteration's normaliser is the post's scalars, which the host
+// waits for only where the stop test reads it or its predecessor (old_sum).
+constexpr int kNormFrom = 99;  // (the iteration before the first stop test)
+int one_rank_norm(psx_engine* e, int iter, double& sss_sum) {
+    if (iter < kNormFrom) return 0;
+    HIPCHK(hipStreamSynchronize(e->stream));
+    sss_sum = logval(e, e->sss->shost->m, e->sss->shost->tot);
+    return 0;
+}
+bool sss_converged(int iter, double old_sum, double sss_sum) {  // sss_postcal.cpp:265-270
+    return iter > kNormFrom && (1 - std::exp(old_sum - sss_sum)) <= 0.001;
+}
+
+// The walk's tail, after its loop left at `iter`: the last post, the timing
+// and the configurations evaluated.
+int sss_finish(psx_engine* e, EvalTimer& timer, int iter, std::chrono::steady_clock::time_point t0,
+               int32_t* iterations_out) {
+    HIPCHK(hipStreamSynchronize(e->stream));  // the last iteration's post (one rank: not waited for in the loop)
+    const auto t1 = std::chrono::steady_clock::now();
+    // (iterations 0 .. iter ran; `iter` itself when it broke out)
+    const int rc = timer.finish(std::min(iter + 1, 1000), e->timing.kernel_ms);
+    if (rc) return rc;
+    if (iterations_out) *iterations_out = iter;
+    e->timing.sweep_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    SetRec s;
+    HIPCHK(hipMemcpy(&s, e->dsacc, sizeof(SetRec), hipMemcpyDeviceToHost));
+    e->timing.configs = (uint64_t)(s.npat + 0.5);
+    return 0;
 }
 
 int run_sss(psx_engine* e, psx_allgather_fn allgather, psx_allgather_dev_fn dgather, void* ctx,
@@ -3256,24 +3315,16 @@ int run_sss(psx_engine* e, psx_allgather_fn allgather, psx_allgather_dev_fn dgat
     const int U = e->U, C = e->maxc;
     if (C > PSX_KMAX) return fail(PSX_ERANGE, "SSS max_causal > 6");
     if (U > kKeyMaxU) return fail(PSX_ERANGE, "SSS: more union SNPs than the set key holds");
-    const int stride = std::max(C, 1);
-    // the most items of an iteration: the current configuration + the largest
-    // neighbourhood (k = C: swaps C (U - C), minus C; k < C: + U - k plus sets)
-    const size_t nmax = (size_t)C * U + C + U + 2;
     const auto tw = std::chrono::steady_clock::now();
-    if ((rc = sss_workspace(e, nmax, world, e->stream))) return rc;
+    if ((rc = sss_workspace(e, world, false))) return rc;
     const double ws_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tw).count();
     SssDev& D = *e->sss;
-    if ((rc = ensure(e->dsrec, e->cap_srec, nmax))) return rc;
-    if ((rc = ensure(e->dmrec, e->cap_mrec, nmax * stride))) return rc;
-    if ((rc = ensure(e->dscore, e->cap_score, nmax))) return rc;
     const SetRec null1 = null_rec(e, 1.0);
     std::mt19937 gen(12345);
     int cur[PSX_KMAX] = {0, 0, 0, 0, 0, 0}, k = 0;  // the current configuration, ascending
     double old_sum = 0;
     int iter;
-    double kms = 0;
-    int ksamples = 0;
+    EvalTimer timer{D.ev, e->stream};
     auto t0 = std::chrono::steady_clock::now();
     std::vector<double> pr;
     // diagnostics (PSX_SSS_PROFILE): host time per phase of the walk, on stderr
@@ -3290,63 +3341,28 @@ int run_sss(psx_engine* e, psx_allgather_fn allgather, psx_allgather_dev_fn dgat
         t = n;
     };
     for (iter = 0; iter < 1000; iter++) {
+        const SssGeom g = psx::sss_geometry(k, U, C);
         SssIter it;
-        for (int j = 0; j < PSX_KMAX; j++) it.cur[j] = j < k ? cur[j] : -1;
-        it.k = k;
-        it.U = U;
-        it.stride = stride;
-        it.num_zero = (U - k) * k;
-        it.num_minus = k;
-        it.num_plus = k < C ? U - k : 0;
-        it.n_nbd = it.num_zero + it.num_minus + it.num_plus;
+        sss_iter_fill(it, cur, k, e, g);
         it.rank = rank;
         it.world = world;
-        it.null_score = e->K + e->L0;
         it.trace = D.trace;
         if (++D.seq == 0) D.seq = 1;  // (tag 0 is a word no iteration wrote)
         it.seq = D.seq;
-        const int n_nbd = it.n_nbd, n_items = n_nbd + 1;
+        const int n_nbd = g.n_nbd, n_items = n_nbd + 1;
         // this rank's contiguous slice of the items
         const int lo = (int)((int64_t)n_items * rank / world), hi = (int)((int64_t)n_items * (rank + 1) / world);
-        // the map stays at load <= 1/2 (every neighbour may be new)
-        if (2 * (D.used + (size_t)n_nbd + 1) > D.cap) {
-            size_t nc = D.cap;
-            while (2 * (D.used + (size_t)n_nbd + 1) > nc) nc <<= 1;
-            MapEntry* nt = nullptr;
-            HIPCHK(psx::dmalloc(&nt, nc * sizeof(MapEntry)));
-            HIPCHK(hipMemsetAsync(nt, 0, nc * sizeof(MapEntry), e->stream));
-            hipLaunchKernelGGL(k_map_rehash, dim3((unsigned)((D.cap + 255) / 256)), dim3(256), 0, e->stream, D.T,
-                               D.cap, nt, (unsigned long long)(nc - 1));
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipStreamSynchronize(e->stream));
-            psx::dfree(D.T);
-            D.T = nt;
-            D.cap = nc;
-        }
+        if ((rc = grow_map(D.T, D.cap, D.used, n_nbd, launch_map_rehash, e->stream))) return rc;
         const unsigned long long mask = D.cap - 1;
         auto tp = std::chrono::steady_clock::now();
-        // plain event records around the eval (the stop event is what the host
-        // waits on): hipExtLaunchKernelGGL's in-packet events cost the host ~12 us
-        // more per launch here (profiles/archive/r03i_sss_host_phases.txt)
-        // The start event only on every kEvEvery-th iteration (an event record is
-        // ~1-2 us of host time): the eval time is sampled there and scaled to all
-        // iterations; the stop event (the host's wait) on every one.
-        hipEvent_t* evp = D.ev + 2 * (iter % SssDev::kRingE);
-        const bool timed = iter % SssDev::kEvEvery == 0;
-        if (iter >= SssDev::kRingE && (iter - SssDev::kRingE) % SssDev::kEvEvery == 0) {  // kRingE iterations ago
-            float ms = 0;
-            HIPCHK(hipEventElapsedTime(&ms, evp[0], evp[1]));
-            kms += ms;
-            ksamples++;
-        }
-        if (timed) HIPCHK(hipEventRecord(evp[0], e->stream));
-        hipLaunchKernelGGL(C <= 5 ? k_sss_eval<5> : k_sss_eval<PSX_KMAX>, dim3((unsigned)n_items), dim3(64), 0,
-                           e->stream, e->dp, it, D.T, mask, lo, hi,
-                           D.rows, D.mark, D.cnt, D.lk, e->dsrec, e->dmrec, e->dscore, world == 1 ? D.hmark : nullptr);
         // (the stop event: the host's wait without the completion word, else only
         // the sampled eval time)
         const bool poll = world == 1 && !event_wait;
-        if (timed || !poll) HIPCHK(hipEventRecord(evp[1], e->stream));
+        if ((rc = timer.begin(iter))) return rc;
+        hipLaunchKernelGGL(C <= 5 ? k_sss_eval<5> : k_sss_eval<PSX_KMAX>, dim3((unsigned)n_items), dim3(64), 0,
+                           e->stream, e->dp, it, D.T, mask, lo, hi,
+                           D.rows, D.mark, D.cnt, D.lk, e->dsrec, e->dmrec, e->dscore, world == 1 ? D.hmark : nullptr);
+        if ((rc = timer.end(iter, !poll))) return rc;
         const unsigned post_blocks = (unsigned)(U + 1 + (world == 1 ? (n_nbd + 255) / 256 : 0));
         hipLaunchKernelGGL(k_sss_post, dim3(post_blocks), dim3(256), 0, e->stream, it, lo, hi, D.rows, D.mark, D.cnt,
                            e->dmrec, e->dsrec, e->dscore, null1, e->dacc, e->dsacc, D.shost, D.hcnt, D.T, mask,
@@ -3360,7 +3376,7 @@ int run_sss(psx_engine* e, psx_allgather_fn allgather, psx_allgather_dev_fn dgat
             // GPU folds the records and inserts the new scores (k_sss_post); it
             // waits for the post only where the stop test needs the normaliser.
             tick(0, tp);
-            if (!poll) HIPCHK(hipEventSynchronize(evp[1]));
+            if (!poll) HIPCHK(hipEventSynchronize(timer.stop(iter)));
             // each neighbour's mark word once it carries this iteration's tag (its
             // weight was acknowledged before it).  An idle stream (eval and post
             // done) with a word still missing is an error.
@@ -3393,111 +3409,64 @@ int run_sss(psx_engine* e, psx_allgather_fn allgather, psx_allgather_dev_fn dgat
                     D.trace[7] = 0;
                 }
             }
-        } else if (dgather) {
-            // the exchange on the device: pack -> the caller's stream-ordered
-            // all-gather -> unpack -> insert, then one synchronisation (no score
-            // copies through the host, no host bytes for the callback)
-            const int per = (n_items + world - 1) / world, wd = 2 + per;
-            if ((size_t)wd * (world + 1) > D.cap_dx) {
-                psx::dfree(D.dx);
-                D.dx = nullptr;
-                D.cap_dx = 0;
-                HIPCHK(psx::dmalloc(&D.dx, sizeof(double) * (size_t)wd * (world + 1)));
-                D.cap_dx = (size_t)wd * (world + 1);
-            }
-            if (2 * world > D.cap_hnorm) {
-                if (D.hnorm) psx::hfree(D.hnorm);
-                D.hnorm = nullptr;
-                HIPCHK(psx::hmalloc(&D.hnorm, sizeof(double) * 2 * world));
-                D.cap_hnorm = 2 * world;
-            }
-            double* const snd = D.dx;
-            double* const rcv = D.dx + wd;
-            hipLaunchKernelGGL(k_sss_pack, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, e->stream, e->dsacc,
-                               e->dscore, lo, hi - lo, per, snd);
-            HIPCHK(hipGetLastError());
-            if (dgather(ctx, snd, rcv, (int64_t)wd * (int64_t)sizeof(double), e->stream))
-                return fail(PSX_EEXCHANGE, "SSS device all-gather callback failed");
-            hipLaunchKernelGGL(k_sss_unpack, dim3((unsigned)((per + 255) / 256), (unsigned)world), dim3(256), 0,
-                               e->stream, rcv, world, n_items, per, D.full, D.hnorm);
-            hipLaunchKernelGGL(k_sss_post, dim3((unsigned)(U + 1 + (n_nbd + 255) / 256)), dim3(256), 0, e->stream, it,
-                               lo, hi, D.rows, D.mark, D.cnt, e->dmrec, e->dsrec, D.full, null1, (Acc5*)nullptr,
-                               (SetRec*)nullptr, (SetRec*)nullptr, (int*)nullptr, D.T, mask, 2, D.lk);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipStreamSynchronize(e->stream));
-            unseen = D.hcnt[kUnseen];
-            double mx = -INFINITY;
-            std::vector<double> part(world, 0.0);
-            for (int r = 0; r < world; r++) {
-                part[r] = logval(e, (int32_t)D.hnorm[2 * r], D.hnorm[2 * r + 1]);
-                if (part[r] != 0.0) mx = std::max(mx, part[r]);
-            }
-            double acc = 0.0;  // the ranks' normalisers, combined in rank order
-            for (int r = 0; r < world; r++)
-                if (part[r] != 0.0) acc += std::exp(part[r] - mx);
-            sss_sum = acc > 0 ? mx + std::log(acc) : 0.0;
         } else {
-            HIPCHK(hipStreamSynchronize(e->stream));
-            unseen = D.hcnt[kUnseen];
-            // one all-gather: [normaliser (m, s), the slice's item scores]; then
-            // every rank inserts all scores and writes the sampling weights
+            // Several ranks: one all-gather of [normaliser (m, s), the slice's item
+            // scores, zero padding]; then every rank inserts all scores and writes
+            // the sampling weights (the post's insert blocks alone: mode 2).
             const size_t per = ((size_t)n_items + world - 1) / world, wd = 2 + per;
-            std::vector<double> snd(wd, 0.0), rcv(wd * world, 0.0);
-            if (hi > lo)
-                HIPCHK(hipMemcpy(snd.data() + 2, e->dscore + lo, (size_t)(hi - lo) * sizeof(double),
-                                 hipMemcpyDeviceToHost));
-            snd[0] = (double)D.shost->m;
-            snd[1] = D.shost->tot;
-            if (allgather(ctx, snd.data(), rcv.data(), (int64_t)(wd * sizeof(double))))
-                return fail(PSX_EEXCHANGE, "SSS all-gather callback failed");
-            double mx = -INFINITY;
-            std::vector<double> part(world, 0.0);
-            for (int r = 0; r < world; r++) {
-                const double* q = rcv.data() + (size_t)r * wd;
-                const size_t rlo = (size_t)n_items * r / world, rn = (size_t)n_items * (r + 1) / world - rlo;
-                std::copy(q + 2, q + 2 + rn, D.hscore + rlo);
-                part[r] = logval(e, (int32_t)q[0], q[1]);
-                if (part[r] != 0.0) mx = std::max(mx, part[r]);
+            std::vector<double> rcv;  // the host exchange's receive blocks
+            if (dgather) {
+                // the exchange on the device: pack -> the caller's stream-ordered
+                // all-gather -> unpack -> insert, then one synchronisation (no score
+                // copies through the host, no host bytes for the callback)
+                if ((rc = ensure(D.dx, D.cap_dx, wd * (world + 1)))) return rc;
+                if ((rc = ensure_host(D.hnorm, D.cap_hnorm, (size_t)2 * world))) return rc;
+                double* const snd = D.dx;
+                double* const drcv = D.dx + wd;
+                hipLaunchKernelGGL(k_sss_pack, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, e->stream, e->dsacc,
+                                   e->dscore, lo, hi - lo, (int)per, snd);
+                HIPCHK(hipGetLastError());
+                if (dgather(ctx, snd, drcv, (int64_t)wd * (int64_t)sizeof(double), e->stream))
+                    return fail(PSX_EEXCHANGE, "SSS device all-gather callback failed");
+                hipLaunchKernelGGL(k_sss_unpack, dim3((unsigned)((per + 255) / 256), (unsigned)world), dim3(256), 0,
+                                   e->stream, drcv, world, n_items, (int)per, D.full, D.hnorm);
+            } else {
+                HIPCHK(hipStreamSynchronize(e->stream));
+                std::vector<double> snd(wd, 0.0);
+                rcv.assign(wd * world, 0.0);
+                if (hi > lo)
+                    HIPCHK(hipMemcpy(snd.data() + 2, e->dscore + lo, (size_t)(hi - lo) * sizeof(double),
+                                     hipMemcpyDeviceToHost));
+                snd[0] = (double)D.shost->m;
+                snd[1] = D.shost->tot;
+                if (allgather(ctx, snd.data(), rcv.data(), (int64_t)(wd * sizeof(double))))
+                    return fail(PSX_EEXCHANGE, "SSS all-gather callback failed");
+                for (int r = 0; r < world; r++) {
+                    const size_t rlo = (size_t)n_items * r / world, rn = (size_t)n_items * (r + 1) / world - rlo;
+                    std::copy(rcv.data() + r * wd + 2, rcv.data() + r * wd + 2 + rn, D.hscore + rlo);
+                }
+                HIPCHK(hipMemcpyAsync(D.full, D.hscore, (size_t)n_items * sizeof(double), hipMemcpyHostToDevice, e->stream));
             }
-            double acc = 0.0;  // the ranks' normalisers, combined in rank order
-            for (int r = 0; r < world; r++)
-                if (part[r] != 0.0) acc += std::exp(part[r] - mx);
-            sss_sum = acc > 0 ? mx + std::log(acc) : 0.0;
-            HIPCHK(hipMemcpyAsync(D.full, D.hscore, (size_t)n_items * sizeof(double), hipMemcpyHostToDevice, e->stream));
-            // the insert blocks alone (block indices past U)
             hipLaunchKernelGGL(k_sss_post, dim3((unsigned)(U + 1 + (n_nbd + 255) / 256)), dim3(256), 0, e->stream, it,
                                lo, hi, D.rows, D.mark, D.cnt, e->dmrec, e->dsrec, D.full, null1, (Acc5*)nullptr,
                                (SetRec*)nullptr, (SetRec*)nullptr, (int*)nullptr, D.T, mask, 2, D.lk);
             HIPCHK(hipGetLastError());
             HIPCHK(hipStreamSynchronize(e->stream));
+            unseen = D.hcnt[kUnseen];
+            sss_sum = dgather ? combine_norms(e, D.hnorm, 2, world) : combine_norms(e, rcv.data(), wd, world);
         }
         D.used += (size_t)unseen;
         if (unseen == 0) break;                                                          // :260-263
         // (one rank: the sampling below runs first and is dropped when the stop
         // test of sss_postcal.cpp:265-270 ends the walk — it only advances gen)
-        sss_sample_next(D.lk, it.num_zero, it.num_minus, it.num_plus, gen, pr, cur, k);
+        psx::sss_sample_next(D.lk, g, gen, pr, cur, k);
         tick(2, tp);
-        if (world == 1 && iter >= 99) {  // the normaliser of this iteration (k_sss_post)
-            HIPCHK(hipStreamSynchronize(e->stream));
-            tick(3, tp);
-            sss_sum = logval(e, D.shost->m, D.shost->tot);
-        }
-        if (iter >= 100 && (1 - std::exp(old_sum - sss_sum)) <= 0.001) break;            // :265-270
+        if (world == 1 && (rc = one_rank_norm(e, iter, sss_sum))) return rc;
+        if (world == 1 && iter >= kNormFrom) tick(3, tp);
+        if (sss_converged(iter, old_sum, sss_sum)) break;
         old_sum = sss_sum;
     }
-    HIPCHK(hipStreamSynchronize(e->stream));  // the last iteration's post (one rank: not waited for in the loop)
-    auto t1 = std::chrono::steady_clock::now();
-    {  // the evals still in the event ring (iterations 0..iter ran; `iter` itself when it broke out)
-        const int ran = std::min(iter + 1, 1000);
-        for (int q = std::max(0, ran - SssDev::kRingE); q < ran; q++) {
-            if (q % SssDev::kEvEvery) continue;
-            float ms = 0;
-            HIPCHK(hipEventElapsedTime(&ms, D.ev[2 * (q % SssDev::kRingE)], D.ev[2 * (q % SssDev::kRingE) + 1]));
-            kms += ms;
-            ksamples++;
-        }
-        if (ksamples) kms *= (double)ran / ksamples;  // the sampled evals' mean, over every iteration
-    }
+    if ((rc = sss_finish(e, timer, iter, t0, iterations_out))) return rc;
     if (D.trace && tph[7] > 0)
         fprintf(stderr, "[psx sss] item-1 eval us: row+probe %.2f, stage %.2f, subsets %.2f, patterns %.2f, "
                 "reductions %.2f, records %.2f (%.0f evals)\n", tph[0] / tph[7], tph[1] / tph[7], tph[2] / tph[7],
@@ -3506,21 +3475,15 @@ int run_sss(psx_engine* e, psx_allgather_fn allgather, psx_allgather_dev_fn dgat
         fprintf(stderr, "[psx sss] %d iterations, host us per iteration: launch %.1f, wait eval %.1f, sampling %.1f, "
                 "wait post %.1f; workspace %.0f us\n", iter, ph[0] / std::max(iter, 1), ph[1] / std::max(iter, 1),
                 ph[2] / std::max(iter, 1), ph[3] / std::max(iter, 1), ws_us);
-    if (iterations_out) *iterations_out = iter;
-    e->timing.sweep_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
-    e->timing.kernel_ms = kms;
-    SetRec s;
-    HIPCHK(hipMemcpy(&s, e->dsacc, sizeof(SetRec), hipMemcpyDeviceToHost));
-    e->timing.configs = (uint64_t)(s.npat + 0.5);
     return 0;
 }
 
-// The walk for max_causal 7 .. PSX_KWIDE, one rank: run_sss's iteration (the
-// same geometry, draws and stop tests) around k_sss_eval_wide / k_sss_post_wide
-// (psx_sss_wide.hip) and the wide set map.  The host waits on the eval's stop
-// event, reads every neighbour's weight and mark from pinned memory and samples
-// the next configuration while the post runs.
+// The walk for max_causal 7 .. PSX_KWIDE, one rank: run_sss's iteration around
+// k_sss_eval_wide / k_sss_post_wide (psx_sss_wide.hip) and the wide set map.
+// The host waits on the eval's stop event, reads every neighbour's weight and
+// mark from pinned memory and samples the next configuration while the post runs.
 int run_sss_wide(psx_engine* e, int32_t* iterations_out) {
+    static_assert(PSX_KWIDE <= psx::kSssMaxK, "sss_sample_next holds the next configuration");
     HIPCHK(hipSetDevice(e->dev));
     e->stat_fresh = false;
     int rc;
@@ -3529,107 +3492,49 @@ int run_sss_wide(psx_engine* e, int32_t* iterations_out) {
     const int U = e->U, C = e->maxc;
     if (C <= PSX_KMAX || C > PSX_KWIDE) return fail(PSX_ERANGE, "wide SSS walk: max_causal outside [7, 10]");
     if (U > kKeyMaxU) return fail(PSX_ERANGE, "SSS: more union SNPs than the set key holds");
-    const int stride = C;
-    const size_t nmax = (size_t)C * U + C + U + 2;  // as run_sss
-    if ((rc = sss_workspace(e, nmax, 1, e->stream, true))) return rc;
+    if ((rc = sss_workspace(e, 1, true))) return rc;
     SssDev& D = *e->sss;
-    if ((rc = ensure(e->dsrec, e->cap_srec, nmax))) return rc;
-    if ((rc = ensure(e->dmrec, e->cap_mrec, nmax * stride))) return rc;
-    if ((rc = ensure(e->dscore, e->cap_score, nmax))) return rc;
     const SetRec null1 = null_rec(e, 1.0);
     std::mt19937 gen(12345);
     int cur[PSX_KWIDE] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, k = 0;  // the current configuration, ascending
-    double old_sum = 0, kms = 0;
-    int iter, ksamples = 0;
+    double old_sum = 0;
+    int iter;
+    EvalTimer timer{D.ev, e->stream};
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<double> pr;
     size_t items = 0;  // PSX_SSS_PROFILE: items launched (D.used: sets evaluated)
     for (iter = 0; iter < 1000; iter++) {
+        const SssGeom g = psx::sss_geometry(k, U, C);
         psx::SssWideIter it;
-        for (int j = 0; j < PSX_KWIDE; j++) it.cur[j] = j < k ? cur[j] : -1;
-        it.k = k;
-        it.U = U;
-        it.stride = stride;
-        it.num_zero = (U - k) * k;
-        it.num_minus = k;
-        it.num_plus = k < C ? U - k : 0;
-        it.n_nbd = it.num_zero + it.num_minus + it.num_plus;
-        it.null_score = e->K + e->L0;
-        const int n_nbd = it.n_nbd;
-        items += (size_t)n_nbd + 1;
-        // the map stays at load <= 1/2 (every neighbour may be new)
-        if (2 * (D.used + (size_t)n_nbd + 1) > D.cap_w) {
-            size_t nc = D.cap_w;
-            while (2 * (D.used + (size_t)n_nbd + 1) > nc) nc <<= 1;
-            psx::WideMapEntry* nt = nullptr;
-            HIPCHK(psx::dmalloc(&nt, nc * sizeof(psx::WideMapEntry)));
-            HIPCHK(hipMemsetAsync(nt, 0, nc * sizeof(psx::WideMapEntry), e->stream));
-            if (psx::launch_wide_map_rehash(D.TW, D.cap_w, nt, (unsigned long long)(nc - 1), e->stream)) {
-                psx::dfree(nt);
-                return fail(PSX_EHIP, "wide SSS map rehash launch failed");
-            }
-            HIPCHK(hipStreamSynchronize(e->stream));
-            psx::dfree(D.TW);
-            D.TW = nt;
-            D.cap_w = nc;
-        }
+        sss_iter_fill(it, cur, k, e, g);
+        items += (size_t)g.n_nbd + 1;
+        if ((rc = grow_map(D.TW, D.cap_w, D.used, g.n_nbd, psx::launch_wide_map_rehash, e->stream))) return rc;
         const unsigned long long mask = D.cap_w - 1;
-        // the event ring of run_sss: the eval time sampled on every kEvEvery-th
-        // iteration, the stop event (the host's wait) on every one
-        hipEvent_t* evp = D.ev + 2 * (iter % SssDev::kRingE);
-        const bool timed = iter % SssDev::kEvEvery == 0;
-        if (iter >= SssDev::kRingE && (iter - SssDev::kRingE) % SssDev::kEvEvery == 0) {
-            float ms = 0;
-            HIPCHK(hipEventElapsedTime(&ms, evp[0], evp[1]));
-            kms += ms;
-            ksamples++;
-        }
-        if (timed) HIPCHK(hipEventRecord(evp[0], e->stream));
+        if ((rc = timer.begin(iter))) return rc;
         if (psx::launch_sss_eval_wide(e->wp, it, D.TW, mask, D.mark, D.cnt, D.keys, D.lk, D.hmk, e->dsrec, e->dmrec,
                                       e->dscore, e->stream))
             return fail(PSX_EHIP, "wide SSS evaluation launch failed");
-        HIPCHK(hipEventRecord(evp[1], e->stream));
+        if ((rc = timer.end(iter, true))) return rc;
         if (psx::launch_sss_post_wide(it, D.mark, D.cnt, D.keys, e->dmrec, e->dsrec, e->dscore, null1, e->dacc,
                                       e->dsacc, D.shost, D.hcnt, D.TW, mask, e->stream))
             return fail(PSX_EHIP, "wide SSS post launch failed");
-        HIPCHK(hipEventSynchronize(evp[1]));
+        HIPCHK(hipEventSynchronize(timer.stop(iter)));
         int unseen = 0;
-        for (int i = 0; i < n_nbd; i++) unseen += D.hmk[i] != -1;
+        for (int i = 0; i < g.n_nbd; i++) unseen += D.hmk[i] != -1;
         D.used += (size_t)unseen;
         if (unseen == 0) break;                                                          // :260-263
         // (the sampling runs first and is dropped when the stop test of
         // sss_postcal.cpp:265-270 ends the walk — it only advances gen)
-        sss_sample_next(D.lk, it.num_zero, it.num_minus, it.num_plus, gen, pr, cur, k);
+        psx::sss_sample_next(D.lk, g, gen, pr, cur, k);
         double sss_sum = 0.0;
-        if (iter >= 99) {  // the normaliser of this iteration (k_sss_post_wide)
-            HIPCHK(hipStreamSynchronize(e->stream));
-            sss_sum = logval(e, D.shost->m, D.shost->tot);
-        }
-        if (iter >= 100 && (1 - std::exp(old_sum - sss_sum)) <= 0.001) break;            // :265-270
+        if ((rc = one_rank_norm(e, iter, sss_sum))) return rc;
+        if (sss_converged(iter, old_sum, sss_sum)) break;
         old_sum = sss_sum;
     }
-    HIPCHK(hipStreamSynchronize(e->stream));  // the last iteration's post
-    const auto t1 = std::chrono::steady_clock::now();
-    {  // the evals still in the event ring
-        const int ran = std::min(iter + 1, 1000);
-        for (int q = std::max(0, ran - SssDev::kRingE); q < ran; q++) {
-            if (q % SssDev::kEvEvery) continue;
-            float ms = 0;
-            HIPCHK(hipEventElapsedTime(&ms, D.ev[2 * (q % SssDev::kRingE)], D.ev[2 * (q % SssDev::kRingE) + 1]));
-            kms += ms;
-            ksamples++;
-        }
-        if (ksamples) kms *= (double)ran / ksamples;  // the sampled evals' mean, over every iteration
-    }
+    if ((rc = sss_finish(e, timer, iter, t0, iterations_out))) return rc;
     if (std::getenv("PSX_SSS_PROFILE"))
         fprintf(stderr, "[psx sss wide] %d iterations, %zu items, %zu unseen neighbours, eval %.3f ms\n", iter, items,
-                D.used, kms);
-    if (iterations_out) *iterations_out = iter;
-    e->timing.sweep_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
-    e->timing.kernel_ms = kms;
-    SetRec s;
-    HIPCHK(hipMemcpy(&s, e->dsacc, sizeof(SetRec), hipMemcpyDeviceToHost));
-    e->timing.configs = (uint64_t)(s.npat + 0.5);
+                D.used, e->timing.kernel_ms);
     return 0;
 }
 }  // namespace

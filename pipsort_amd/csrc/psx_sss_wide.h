@@ -1,13 +1,29 @@
 // psx_sss_wide.h — the SSS walk's device side for max_causal 7 .. PSX_KWIDE
 // (psx_sss_wide.hip): the wide set map, one iteration's evaluation of the
 // current configuration and its neighbourhood on the wide-set evaluator, and
-// the post stage.  The host walk (psx_run_sss_wide) is in psx_engine.hip.
+// the post stage; and what both walks' device code shares (the set keys' field
+// width, the hash mixer, the iteration counters).  The host walk is in
+// psx_engine.hip (run_sss_wide, on the helpers it shares with run_sss); the
+// neighbourhood geometry, the neighbour order and the draw of the next
+// configuration are in psx_sample.h.
 #ifndef PSX_SSS_WIDE_H
 #define PSX_SSS_WIDE_H
 
 #include "psx_wide.h"
 
 namespace psx {
+
+// a sorted set as words of three (index + 1) fields: two words for the narrow
+// walk's sets of <= PSX_KMAX members, four for <= PSX_KWIDE
+constexpr int kKeyBits = 21;
+
+__host__ __device__ inline unsigned long long mix64(unsigned long long x) {
+    x ^= x >> 30;
+    x *= 0xbf58476d1ce4e5b9ULL;
+    x ^= x >> 27;
+    x *= 0x94d049bb133111ebULL;
+    return x ^ (x >> 31);
+}
 
 // A sorted set of up to PSX_KWIDE members as four words of three (index + 1)
 // fields of 21 bits (the narrow walk's packing, extended), its score, and the
@@ -28,8 +44,12 @@ struct SssWideIter {
     double null_score;   // K + L0: a null configuration's L
 };
 
-// the iteration counters (device cnt[], copied to pinned host memory by the post)
-enum { kSwUnseen = 0, kSwNulls = 1, kSwCurPos = 2, kSwCurNull = 3, kSwNCnt = 4 };
+// The iteration counters (device cnt[]): the eval's block 0 writes the current
+// configuration's two (kCurPos: 0 if it is evaluated, else -1; kCurNull: 1 if
+// it is an unseen null configuration), the post's scalar block counts the
+// unseen neighbours and null configurations from mark[] (no contended atomics
+// in the eval) and copies all four to pinned host memory.
+enum { kUnseen = 0, kNulls = 1, kCurPos = 2, kCurNull = 3, kNCnt = 4 };
 
 // Items 0 .. n_nbd: row, key, probe of T, and the evaluation of every unseen
 // set of 1 .. stride members (stride = max_causal, 7 .. PSX_KWIDE).  Per item p:

@@ -30,16 +30,8 @@ extern "C" __device__ __attribute__((const)) int __ockl_wfred_add_i32(int);
 namespace psx {
 namespace {
 
-constexpr int kKeyBits = 21;  // three (index + 1) fields per 64-bit word
 static_assert(3 * 4 >= KW, "four key words hold PSX_KWIDE fields");
 
-__device__ inline unsigned long long mix64(unsigned long long x) {
-    x ^= x >> 30;
-    x *= 0xbf58476d1ce4e5b9ULL;
-    x ^= x >> 27;
-    x *= 0x94d049bb133111ebULL;
-    return x ^ (x >> 31);
-}
 __device__ inline unsigned long long wmap_slot(const unsigned long long (&w)[4], unsigned long long mask) {
     unsigned long long h = 0;
 #pragma unroll
@@ -164,8 +156,8 @@ __global__ __launch_bounds__(kThreads) void k_sss_eval_wide(WideProb W, SssWideI
                 if (mk != p) lk_host[i] = seen ? v : it.null_score;  // (an unseen set's after its evaluation)
             }
         } else if (t == 0) {
-            cnt[kSwCurPos] = (seen || n == 0) ? -1 : 0;  // a null current configuration is counted, not evaluated
-            cnt[kSwCurNull] = (!seen && n == 0) ? 1 : 0;
+            cnt[kCurPos] = (seen || n == 0) ? -1 : 0;  // a null current configuration is counted, not evaluated
+            cnt[kCurNull] = (!seen && n == 0) ? 1 : 0;
         }
         if (t == 0) sh.ok = !seen && n > 0;
     }
@@ -293,7 +285,7 @@ __global__ __launch_bounds__(256) void k_sss_post_wide(SssWideIter it, const int
             SetRec g = *sacc;
             for (int q = 0; q < 4; q++) fold_set(g, ss[q]);
             const int unseen = sc[0][0] + sc[0][1] + sc[0][2] + sc[0][3];
-            const int nn = sc[1][0] + sc[1][1] + sc[1][2] + sc[1][3] + cnt[kSwCurNull];
+            const int nn = sc[1][0] + sc[1][1] + sc[1][2] + sc[1][3] + cnt[kCurNull];
             if (nn > 0) {
                 SetRec x = null1;  // null1 scaled to nn null configurations
                 x.tot *= nn;
@@ -304,10 +296,10 @@ __global__ __launch_bounds__(256) void k_sss_post_wide(SssWideIter it, const int
             }
             *sacc = g;
             *sacc_host = g;
-            cnt_host[kSwUnseen] = unseen;
-            cnt_host[kSwNulls] = nn;
-            cnt_host[kSwCurPos] = cnt[kSwCurPos];
-            cnt_host[kSwCurNull] = cnt[kSwCurNull];
+            cnt_host[kUnseen] = unseen;
+            cnt_host[kNulls] = nn;
+            cnt_host[kCurPos] = cnt[kCurPos];
+            cnt_host[kCurNull] = cnt[kCurNull];
         }
         return;
     }
