@@ -320,12 +320,15 @@ int psx_merge_partials(psx_engine *e, const void *device_src, int32_t count);
 int psx_fold_partials_host(const void *src, int32_t count, int64_t image_bytes, void *dst);
 
 /* Host-only: union subsets and configurations of causal-set level k (1..c)
- * that shard `rank` of `world` evaluates in psx_run_exhaustive. */
+ * that shard `rank` of `world` evaluates in psx_run_exhaustive: levels 2, 3
+ * and 4 by the tiled sweeps' unit plans (level 4: unless PSX_K4_GENERIC=1 or
+ * its records would pass 1 GiB), the others by equal slices of the
+ * lexicographic enumeration. */
 int psx_shard_stats(const psx_problem *prob, int32_t k, int32_t rank, int32_t world, uint64_t *union_sets,
                     double *configs);
 
 /* Host-side diagnostics (no device): the host time of building level k's
- * (2 or 3) unit plan and record CSR for shard rank of world, every union SNP
+ * (2, 3 or 4; n_union >= k) unit plan for shard rank of world, every union SNP
  * in both studies; *n_units / *n_records the plan's size. */
 int psx_plan_build_ms(int32_t n_union, int32_t k, int32_t rank, int32_t world, double *ms, int32_t *n_units,
                       int64_t *n_records);

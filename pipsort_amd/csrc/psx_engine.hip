@@ -2265,6 +2265,7 @@ int psx_warmup_for(int device, int32_t max_causal, int32_t configs_file) {
         return fail(PSX_EHIP, "warm-up: sweep device code did not load");
     t[4] = now();
     if (max_causal >= 3 && psx::warm_module_sweep3()) return fail(PSX_EHIP, "warm-up: k = 3 device code did not load");
+    if (max_causal >= 4 && psx::warm_module_sweep4()) return fail(PSX_EHIP, "warm-up: k = 4 device code did not load");
     // (sets of 7 .. 10 members: the wide evaluator and the wide SSS walk, small code objects both)
     if (max_causal > PSX_KMAX && (psx::warm_module_wide() || psx::warm_module_sss_wide()))
         return fail(PSX_EHIP, "warm-up: wide-set device code did not load");
@@ -3725,7 +3726,8 @@ int psx_plan_csr_selftest(int32_t n_union, const uint8_t* presence, int32_t k, i
 
 int psx_plan_build_ms(int32_t n_union, int32_t k, int32_t rank, int32_t world, double* ms, int32_t* n_units,
                       int64_t* n_records) {
-    if (n_union < 3 || (k != 2 && k != 3) || world < 1 || rank < 0 || rank >= world || !ms || !n_units || !n_records)
+    if (n_union < 3 || k < 2 || k > 4 || n_union < k || world < 1 || rank < 0 || rank >= world || !ms || !n_units ||
+        !n_records)
         return fail(PSX_EINVAL, "bad arguments");
     long nr = 0;
     int nu = 0;

@@ -1,4 +1,4 @@
-// psx_sweep.h — tiled exhaustive sweep over union subsets of size k in {2, 3}
+// psx_sweep.h — tiled exhaustive sweep over union subsets of size k in {2, 3, 4}
 // (the dominant levels of PostCal::computeTotalLikelihood, postcal.cpp:716-1092).
 #ifndef PSX_SWEEP_H
 #define PSX_SWEEP_H
@@ -123,6 +123,7 @@ constexpr int kMaxChunkA3 = 4;
 // words per unit of the PSX_UNIT_TRACE dump (tools/unit_trace.py)
 constexpr int kTraceWords = 16;
 struct Level2Blocks;  // psx_sweep_dev.h
+struct TileArgs;      // psx_sweep_dev.h
 int launch_sweep3(bool allpres, const Sweep3Args& A, int n_units, const int4* units, Acc5* rec, SetRec* srec,
                   int rec_stride, int* flag, const int* pos, hipStream_t st, const Level2Blocks* l2, hipEvent_t ev0 = nullptr,
                   hipEvent_t ev1 = nullptr);
@@ -142,6 +143,22 @@ int launch_bc3_rowsum(int ntile, const double2* mu01, const int2* n, double2* sm
 int launch_bc3_colsum(int ntile, const double2* mu01, const int2* n, double2* sm, int2* sn, hipStream_t st);
 // out[i] = (a[i], b[i])
 int launch_interleave2(const double* a, const double* b, size_t n, double2* out, hipStream_t st);
+
+// The k = 4 sweep (psx_sweep4.hip): units {p, q0, q1, B | T << 16}, records
+// unit-major (slots 0..63 c, 64..127 b, 128 p, 129.. one per q of the unit).
+// Most q per unit: the kernel stages the unit's per-q scalars in LDS.
+constexpr int kMaxChunkQ4 = 16;
+// dispatch rounds of the wave slots per shard the q-chunk is sized for
+constexpr double kK4Rounds = 4.0;
+// the level's records (of the world-1 plan) above which level 4 stays on the generic route
+constexpr double kK4RecordCap = 1024.0 * 1024.0 * 1024.0;
+// exact = true, or a prior without unshared weight: the pattern-walk variant
+int launch_sweep4(bool exact, const TileArgs& A, int n_units, const int4* units, Acc5* rec, SetRec* srec,
+                  int rec_stride, int* flag, hipStream_t st);
+// keys[slot] = the SNP of record slot `slot` (-1: none)
+int launch_keys4(const int4* units, int n_units, int rec_stride, int U, int* keys, hipStream_t st);
+// bytes of the level-4 records of the world-1 plan (sweep_supports' cap)
+double plan4_record_bytes(int U);
 
 // a level's plan built ahead on a host thread (plan_prefetch)
 struct PlanJob {
@@ -213,7 +230,7 @@ struct SweepPlanCache {
 };
 
 bool sweep_supports(int k, int U);
-struct PlanUnit { int a0, a1, B, T; double work; int j0 = 0, j1 = 64; };
+struct PlanUnit { int a0, a1, B, T; double work; int j0 = 0, j1 = 64; int p = 0; };  // p: k = 4 (a0, a1 = q0, q1)
 int plan_units(int k, int U, int ldg, int rank, int world, const unsigned char* pres_host,
                std::vector<PlanUnit>& mine, int& ca, double& sets, double& configs, double& bytes);
 // plan-shaping knobs of the k = 3 decomposition (environment, read once)
@@ -264,6 +281,7 @@ const char* sweep_error();
 // device code of the sweep translation units, loaded ahead of first use (psx_warmup)
 int warm_module_sweep();
 int warm_module_sweep3();
+int warm_module_sweep4();
 
 }  // namespace psx
 #endif

@@ -1,4 +1,4 @@
-// psx_sweep.hip — tiled exhaustive sweep (levels k = 2, 3) and record merges.
+// psx_sweep.hip — tiled exhaustive sweep (levels k = 2, 3; host side of k = 4) and record merges.
 //
 // Work decomposition (DESIGN.md "Sweep kernel"): union indices are cut into
 // 64-wide blocks.  A unit is (a-chunk, B, T): one wave, lane t owns
@@ -222,7 +222,20 @@ int launch_merge_sets(const SetRec* rec, long n, const SetRec& extra, SetRec* ac
 // ---------------------------------------------------------------------------
 // Host planning
 // ---------------------------------------------------------------------------
-bool sweep_supports(int k, int U) { return (k == 2 || k == 3) && U >= 3; }
+// PSX_K4_GENERIC = 1 (read once per process; the same on every rank of a job)
+// keeps level 4 on the generic evaluator: A/B timing and an escape hatch
+static bool k4_generic() {
+    static const bool g = [] {
+        const char* e = std::getenv("PSX_K4_GENERIC");
+        return e && std::atoi(e) != 0;
+    }();
+    return g;
+}
+
+bool sweep_supports(int k, int U) {
+    if (k == 4) return U >= 4 && U < (1 << 20) && !k4_generic() && plan4_record_bytes(U) <= kK4RecordCap;
+    return (k == 2 || k == 3) && U >= 3;
+}
 
 // algorithmic bytes of one union set's configurations:
 // 8 * sum over assignments of sum_s (|C_s|^2 + |C_s|)
@@ -245,10 +258,131 @@ static double set_alg_bytes(int k, const int* memb /*bit0 study0, bit1 study1*/)
     return tot;
 }
 
+// ---- k = 4: units (p, [q0, q1), B, T) ---------------------------------------
+// Lane t of a unit owns b = 64B + t and walks c over block T, so the unit's
+// (p, q) lie below b: q < qhi(B) = min(64B + 63, U - 2), p < q.  Every p of a
+// tile cuts its q range (p, qhi) into chunks of cq.
+constexpr int kPlan4Version = 1;  // the k = 4 decomposition's rules, in the plan hash
+constexpr double kUnit4W = 0.15;  // fixed cost of a unit in q walks (prologue, records)
+
+static int qhi4(int B, int U) { return std::min(64 * B + 63, U - 2); }  // q < b <= U - 2
+
+// the q-chunk of (U, world): kK4Rounds dispatch rounds of the 2 x 4 x 256 wave
+// slots of an MI355X per shard (a constant, not a device query: every rank must
+// cut the same unit list), at most kMaxChunkQ4
+static int chunk_q4(int U, int world) {
+    const int nb = (U + 63) / 64;
+    double pairs = 0;
+    for (int B = 0; B < nb; B++) {
+        const double h = qhi4(B, U);
+        pairs += (nb - B) * h * (h - 1) / 2;
+    }
+    const double target = kK4Rounds * 2.0 * 4.0 * 256.0;
+    const long cq = std::lround(pairs / (target * world));
+    return (int)std::max(1L, std::min((long)kMaxChunkQ4, cq));
+}
+
+// units of the whole level at chunk cq, in closed form per B
+static double units4(int U, int cq) {
+    const int nb = (U + 63) / 64;
+    double n = 0;
+    for (int B = 0; B < nb; B++) {
+        const long M = qhi4(B, U) - 1;  // sum over p of ceil((qhi - 1 - p) / cq) = sum_{m = 1..M} ceil(m / cq)
+        if (M <= 0) continue;
+        const long full = M / cq, rem = M % cq;
+        n += (double)(nb - B) * ((double)cq * full * (full + 1) / 2 + (double)rem * (full + 1));
+    }
+    return n;
+}
+
+// The cap is judged on the world-1 plan, so sweep_supports(4, U) depends on U
+// alone and every rank of a job takes the same route (a shard of a larger world
+// holds about the same number of units with a shorter stride).
+double plan4_record_bytes(int U) {
+    const int cq = chunk_q4(U, 1);
+    return units4(U, cq) * (129.0 + cq) * sizeof(Acc5);
+}
+
+static int plan_units4(int U, int ldg, int rank, int world, const unsigned char* pres_host,
+                       std::vector<PlanUnit>& mine, int& ca, double& sets, double& configs, double& bytes) {
+    const int nb = (U + 63) / 64;
+    const int cq = chunk_q4(U, world);
+    ca = cq;
+    // the shard's contiguous, equal-work slice of the enumeration (T, B, p, q0),
+    // found without materialising the other shards' units
+    const double wsum = units4(U, cq) * kUnit4W + [&] {
+        double pairs = 0;
+        for (int B = 0; B < nb; B++) {
+            const double h = qhi4(B, U);
+            pairs += (nb - B) * h * (h - 1) / 2;
+        }
+        return pairs;
+    }();
+    const double lo = wsum * rank / world, hi = wsum * (rank + 1) / world;
+    double run = 0;
+    mine.clear();
+    for (int T = 0; T < nb; T++)
+        for (int B = 0; B <= T; B++) {
+            const int qhi = qhi4(B, U);
+            for (int p = 0; p + 1 < qhi; p++)
+                for (int q0 = p + 1; q0 < qhi; q0 += cq) {
+                    const int q1 = std::min(q0 + cq, qhi);
+                    const double w = kUnit4W + (q1 - q0);
+                    const double mid = run + 0.5 * w;
+                    if (mid >= lo && mid < hi) {
+                        PlanUnit u{q0, q1, B, T, w};
+                        u.p = p;
+                        mine.push_back(u);
+                    }
+                    run += w;
+                }
+        }
+    // exact counts from per-class prefix counts (classes 1: study 0, 2: study 1, 3: both)
+    double bytes_cls[4][4][4][4];
+    for (int x = 1; x < 4; x++)
+        for (int y = 1; y < 4; y++)
+            for (int z = 1; z < 4; z++)
+                for (int v = 1; v < 4; v++) {
+                    const int m4[4] = {x, y, z, v};
+                    bytes_cls[x][y][z][v] = set_alg_bytes(4, m4);
+                }
+    const double wcls[4] = {0, 1, 1, 3};
+    std::vector<int> pref[4];
+    for (int x = 1; x < 4; x++) {
+        pref[x].assign(U + 1, 0);
+        for (int i = 0; i < U; i++) pref[x][i + 1] = pref[x][i] + (pres_host[i] == x);
+    }
+    sets = 0; bytes = 0; configs = 0;
+    for (const PlanUnit& u : mine) {
+        const int x = pres_host[u.p];
+        if (x == 0) continue;
+        for (int t = 0; t < 64; t++) {
+            const int b = 64 * u.B + t;
+            if (b >= U) break;
+            const int z = pres_host[b];
+            const int q1 = std::min(u.a1, b);
+            const int c_lo = (u.B < u.T) ? 64 * u.T : b + 1, c_hi = std::min(64 * u.T + 64, U);
+            if (z == 0 || q1 <= u.a0 || c_hi <= c_lo) continue;
+            for (int y = 1; y < 4; y++) {
+                const double nq = pref[y][q1] - pref[y][u.a0];
+                if (nq == 0) continue;
+                for (int v = 1; v < 4; v++) {
+                    const double n = nq * (pref[v][c_hi] - pref[v][c_lo]);
+                    sets += n;
+                    bytes += n * bytes_cls[x][y][z][v];
+                    configs += n * wcls[x] * wcls[y] * wcls[z] * wcls[v];
+                }
+            }
+        }
+    }
+    return 0;
+}
+
 // Host-only decomposition of level k into wave units for shard (rank, world),
 // plus exact union-set / configuration counts and algorithmic bytes.
 int plan_units(int k, int U, int ldg, int rank, int world, const unsigned char* pres_host,
                std::vector<PlanUnit>& mine, int& ca, double& sets, double& configs, double& bytes) {
+    if (k == 4) return plan_units4(U, ldg, rank, world, pres_host, mine, ca, sets, configs, bytes);
     const int nblk = ldg / 64;
     std::vector<PlanUnit> all;
     if (k == 3) {
@@ -393,7 +527,7 @@ uint64_t plan_knobs_hash() {
         for (size_t i = 0; i < n; i++) h = (h ^ ((const unsigned char*)p)[i]) * 1099511628211ull;
     };
     mix(v, sizeof(v));
-    const int c[4] = {PSX_K3_WAVES, kMaxChunkA3, PSX_KMAX, kPlanVersion};
+    const int c[6] = {PSX_K3_WAVES, kMaxChunkA3, PSX_KMAX, kPlanVersion, kPlan4Version, kMaxChunkQ4};
     mix(c, sizeof(c));
     return h;
 }
@@ -617,6 +751,23 @@ static int upload_plan(SweepPlan& P, SweepPlanCache& C, hipStream_t st) {
     P.d_pos = P.d_csr;
     P.d_dptr = P.d_csr + n;
     P.d_gidx = P.d_csr + n + P.U + 1;
+    if (P.k == 4) {
+        // unit-major records at their slots; the keys (the SNP of every slot) take
+        // the pos region, which the k = 4 kernel does not read
+        int* keys = P.d_csr;
+        P.d_pos = nullptr;
+        P.csr_pos = false;
+        if (launch_keys4(P.d_units, P.n_units, P.rec_stride, P.U, keys, st) ||
+            csr_from_keys_device(keys, (long)n, P.U, const_cast<int*>(P.d_dptr), const_cast<int*>(P.d_gidx),
+                                 C.csr_scratch, st)) {
+            g_sweep_err = "plan CSR on the device failed";
+            return -1;
+        }
+        SWCHK(hipStreamSynchronize(st));
+        std::vector<int4>().swap(P.h_units);
+        P.uploaded = true;
+        return 0;
+    }
     P.csr_pos = records_at_csr_positions(P.world);
     if (plan_csr_device(P.d_units, P.n_units, P.rec_stride, P.k, P.variant, P.pad, P.U, const_cast<int*>(P.d_pos),
                         const_cast<int*>(P.d_dptr), const_cast<int*>(P.d_gidx), C.csr_scratch, st, P.csr_pos)) {
@@ -687,7 +838,7 @@ static int build_plan(SweepPlan& P, int k, int U, int ldg, int rank, int world, 
                 g_sweep_err = "k = 3 unit a-range outside 1.." + std::to_string(kMaxChunkA3);
                 return -1;
             }
-    P.rec_stride = (k == 3) ? 128 + ca : 128;
+    P.rec_stride = (k == 4) ? 129 + ca : (k == 3) ? 128 + ca : 128;
     P.n_units = (int)mine.size();
     P.union_sets = (uint64_t)sets;
     P.alg_bytes = bytes;
@@ -697,14 +848,17 @@ static int build_plan(SweepPlan& P, int k, int U, int ldg, int rank, int world, 
     // r04t, 131.8 in r04ag): kept at or below the last count, so a bench line without PMC
     // counters of its own build cannot overstate the FP64 rate; k = 2 by the
     // round-1 ratio of VALU work per set.  bench.py reports it only as a model.
-    P.flops = sets * (k == 3 ? 131.0 : 110.0);
+    // (k = 4: counted from the step's instruction mix, 14 pivots with their rsqrt_nr
+    // and split2 plus the Kronecker sums; a model until PMC counts replace it)
+    P.flops = sets * (k == 4 ? 1500.0 : k == 3 ? 131.0 : 110.0);
     P.pad = variant ? ldg - U : 0;  // record keys of variant 1 are in v space
     // variant 1 packs the b-walk step range of (half) units into the high bits
     P.h_units.resize(P.n_units);
     for (int i = 0; i < P.n_units; i++)
         P.h_units[i] = variant ? make_int4(mine[i].a0, mine[i].a1, mine[i].B | (mine[i].j0 << 16),
                                            mine[i].T | (mine[i].j1 << 16))
-                               : make_int4(mine[i].a0, mine[i].a1, mine[i].B, mine[i].T);
+                       : k == 4 ? make_int4(mine[i].p, mine[i].a0, mine[i].a1, mine[i].B | (mine[i].T << 16))
+                                : make_int4(mine[i].a0, mine[i].a1, mine[i].B, mine[i].T);
     // Records at their CSR positions (since r06): the kernels write record slot
     // i at pos[i] (-1: no SNP), each SNP's run contiguous in slot order, so the
     // pass merge reads it coalesced (r01-r05 wrote slot i at i, unit-major, and
@@ -986,8 +1140,12 @@ int sweep_level(SweepPlanCache& C, int k, int U, int ldg, int rank, int world, h
     if (sweep_kernel(C, *PP, st, a, nullptr, exact, nullptr, nullptr)) return -1;
     SweepPlan& P = *PP;
     if (P.n_units == 0) return 0;
-    hipLaunchKernelGGL(k_merge_rows, dim3(P.U), dim3(256), 0, st, P.d_rec, P.d_dptr, P.d_gidx, acc);
-    SWCHK(hipGetLastError());
+    if (k == 4) {
+        if (launch_merge_dptr(P.d_rec, P.d_dptr, P.d_gidx, P.U, acc, st)) return -1;
+    } else {
+        hipLaunchKernelGGL(k_merge_rows, dim3(P.U), dim3(256), 0, st, P.d_rec, P.d_dptr, P.d_gidx, acc);
+        SWCHK(hipGetLastError());
+    }
     SetRec none = set_zero();
     if (launch_merge_sets(P.d_srec, P.n_units, none, sacc, st)) return -1;
     SWCHK(hipEventRecord(P.ev[2], st));
@@ -1009,7 +1167,7 @@ static TileArgs tile_args(const SweepPlanCache& C, const SweepArgs& a, int k, in
     A.rsd[0] = 1.0 / std::sqrt(a.d0); A.rsd[1] = 1.0 / std::sqrt(a.d1);
     A.U = U; A.ldg = ldg;
     A.Ck = a.Ck[k];
-    for (int n = 0; n < 4; n++) A.pit[n] = (n <= k) ? a.pit[k * a.pit_ld + n] : 0.0;
+    for (int n = 0; n < 5; n++) A.pit[n] = (n <= k) ? a.pit[k * a.pit_ld + n] : 0.0;
     return A;
 }
 
@@ -1081,6 +1239,8 @@ int sweep_kernel(SweepPlanCache& C, SweepPlan& P, hipStream_t st, const SweepArg
                 std::fclose(f);
             }
         }
+    } else if (k == 4) {
+        if (launch_sweep4(exact, A, P.n_units, P.d_units, rec, srec, P.rec_stride, flag, st)) SWCHK(hipGetLastError());
     } else if (k == 3)
         hipLaunchKernelGGL((k_sweep<3, true>), g, blk, 0, st, A, P.d_units, rec, srec, P.rec_stride, flag, P.d_pos);
     else if (!exact)

@@ -20,7 +20,7 @@ struct TileArgs {
     const unsigned char* pres;
     double d[2], rsd[2];   // d_s and d_s^{-1/2}
     int U, ldg, Ck;
-    double pit[4];
+    double pit[5];         // prior weight by shared members, level k's row (k <= 4)
 };
 
 // level-2 units launched as extra blocks of the k = 3 fast kernel

@@ -14,58 +14,22 @@ struct SweepUnitSmem {
     Acc5 sacc[2][64];  // [0] a, [1] b accumulators, lane-owned
 };
 
-// One union set: per-study subset weights (n, mu) for the 2^K subsets (bit j =
-// member j), zero-weighted where a member is absent from the study.  Folds the
-// 3^K assignments (postcal.cpp:907-1030) into per-member records and the set's
-// scalar record.
-//
-// notSharedLL (member j unshared) sums over assignment groups whose maximum sits
-// Gll - GN_j bits below the set maximum.  The fast variant rescales the group
-// sum by that gap (exact while the gap is <= 900 bits, i.e. unless j's
-// quadratic gain exceeds ~900 bits in both studies) and raises *flag otherwise;
-// the host then reruns the level with EXACT = true, which rescales each group's
-// subset weights to the group's own maximum.
+// The records of one union set from its assignment sums: Sw[j][x] / Sl[j][x] sum
+// the prior-weighted / plain weights of the assignments with member j in study
+// 0 only (x = 0), study 1 only (1) or both (2), E0 / E1 are the subset weights
+// pre-scaled to each study's full-set exponent.  Shared by the pattern walk
+// below and the k = 4 sweep's Kronecker sums (psx_sweep4.hip).
 template <int K, bool EXACT>
-__device__ __forceinline__ void fold_set_patterns(const TileArgs& A, const int (&nn)[2][1 << K],
-                                                  const double (&mu)[2][1 << K], int Sm0, int Sm1,
-                                                  double wcount, int* flag, Acc5 (&out)[K], SetRec& sr) {
+__device__ __forceinline__ void fold_set_finish(const TileArgs& A, const int (&nn)[2][1 << K],
+                                                const double (&mu)[2][1 << K], int Sm0, int Sm1,
+                                                const double (&E0)[1 << K], const double (&E1)[1 << K],
+                                                const double (&Sw)[K][3], const double (&Sl)[K][3], double wcount,
+                                                int* flag, Acc5 (&out)[K], SetRec& sr) {
     constexpr int NS = 1 << K;
     constexpr int FULL = NS - 1;
-    constexpr int NP = (K == 2) ? 9 : 27;
-    // pre-scale each study to its own top exponent (exact powers of two)
+    constexpr int NP = (K == 2) ? 9 : (K == 3) ? 27 : 81;
     const int nb0 = nn[0][FULL], nb1 = nn[1][FULL];
-    double E0[NS], E1[NS];
-#pragma unroll
-    for (int T = 0; T < NS; T++) {
-        E0[T] = ((T & ~Sm0) == 0) ? ldexp(mu[0][T], nn[0][T] - nb0) : 0.0;
-        E1[T] = ((T & ~Sm1) == 0) ? ldexp(mu[1][T], nn[1][T] - nb1) : 0.0;
-    }
-    const int Gll = nb0 + nb1;  // E0 E1 < 4: values stay below 2^2 relative to Gll
-    double Sw[K][3], Sl[K][3];
-#pragma unroll
-    for (int j = 0; j < K; j++)
-#pragma unroll
-        for (int x = 0; x < 3; x++) Sw[j][x] = Sl[j][x] = 0.0;
-#pragma unroll
-    for (int p = 0; p < NP; p++) {
-        int c0 = 0, c1 = 0, nsh = 0, r = p;
-        int x[K];
-#pragma unroll
-        for (int j = 0; j < K; j++) {
-            x[j] = r % 3;  // 0: study0 only, 1: study1 only, 2: both
-            r /= 3;
-            if (x[j] != 1) c0 |= 1 << j;
-            if (x[j] != 0) c1 |= 1 << j;
-            if (x[j] == 2) nsh++;
-        }
-        const double wll = E0[c0] * E1[c1];
-        const double w = wll * A.pit[nsh];
-#pragma unroll
-        for (int j = 0; j < K; j++) {
-            Sw[j][x[j]] += w;
-            Sl[j][x[j]] += wll;
-        }
-    }
+    const int Gll = nb0 + nb1;
     // notSharedLL groups: member j unshared, max pattern 2^{GN_j - 2}
     int GN[K], dmax = 0;
 #pragma unroll
@@ -133,6 +97,60 @@ __device__ __forceinline__ void fold_set_patterns(const TileArgs& A, const int (
     sr.pad = 0;
     sr.score = 1e300;
     sr.npat = wcount;
+}
+
+// One union set: per-study subset weights (n, mu) for the 2^K subsets (bit j =
+// member j), zero-weighted where a member is absent from the study.  Folds the
+// 3^K assignments (postcal.cpp:907-1030) into per-member records and the set's
+// scalar record.
+//
+// notSharedLL (member j unshared) sums over assignment groups whose maximum sits
+// Gll - GN_j bits below the set maximum.  The fast variant rescales the group
+// sum by that gap (exact while the gap is <= 900 bits, i.e. unless j's
+// quadratic gain exceeds ~900 bits in both studies) and raises *flag otherwise;
+// the host then reruns the level with EXACT = true, which rescales each group's
+// subset weights to the group's own maximum.
+template <int K, bool EXACT>
+__device__ __forceinline__ void fold_set_patterns(const TileArgs& A, const int (&nn)[2][1 << K],
+                                                  const double (&mu)[2][1 << K], int Sm0, int Sm1,
+                                                  double wcount, int* flag, Acc5 (&out)[K], SetRec& sr) {
+    constexpr int NS = 1 << K;
+    constexpr int FULL = NS - 1;
+    constexpr int NP = (K == 2) ? 9 : (K == 3) ? 27 : 81;
+    // pre-scale each study to its own top exponent (exact powers of two)
+    const int nb0 = nn[0][FULL], nb1 = nn[1][FULL];
+    double E0[NS], E1[NS];
+#pragma unroll
+    for (int T = 0; T < NS; T++) {
+        E0[T] = ((T & ~Sm0) == 0) ? ldexp(mu[0][T], nn[0][T] - nb0) : 0.0;
+        E1[T] = ((T & ~Sm1) == 0) ? ldexp(mu[1][T], nn[1][T] - nb1) : 0.0;
+    }
+    double Sw[K][3], Sl[K][3];  // (E0 E1 < 4: values stay below 2^2 relative to nb0 + nb1)
+#pragma unroll
+    for (int j = 0; j < K; j++)
+#pragma unroll
+        for (int x = 0; x < 3; x++) Sw[j][x] = Sl[j][x] = 0.0;
+#pragma unroll
+    for (int p = 0; p < NP; p++) {
+        int c0 = 0, c1 = 0, nsh = 0, r = p;
+        int x[K];
+#pragma unroll
+        for (int j = 0; j < K; j++) {
+            x[j] = r % 3;  // 0: study0 only, 1: study1 only, 2: both
+            r /= 3;
+            if (x[j] != 1) c0 |= 1 << j;
+            if (x[j] != 0) c1 |= 1 << j;
+            if (x[j] == 2) nsh++;
+        }
+        const double wll = E0[c0] * E1[c1];
+        const double w = wll * A.pit[nsh];
+#pragma unroll
+        for (int j = 0; j < K; j++) {
+            Sw[j][x[j]] += w;
+            Sl[j][x[j]] += wll;
+        }
+    }
+    fold_set_finish<K, EXACT>(A, nn, mu, Sm0, Sm1, E0, E1, Sw, Sl, wcount, flag, out, sr);
 }
 
 
